@@ -6,14 +6,21 @@ original 640x640 size (pf_postprocess_batch) -> per-image ParamNet scalars (+ al
 scalars over RCCL when N > 1).  Workload = BASELINE.json configs[2]: batch 32, 640x640,
 Paramnet-360Cities-edina-centered, random-init (seeded synthetic) weights, synthetic images.
 The reference's host-side PIL resize (perspectivefields.py:201) happens before the timed region.
-Reported next to `value` (never as `value`):
+A plain run only sets up, warms up, times --steps steps and prints the line (metric, value, unit, higher_is_better,
+dtype, ms_per_step = milliseconds of one timed step).  With --full it also reports, next to `value` (never as `value`):
+  * `roofline` and the per-class figures: HIP events around the dominant launches in every timed step, plus one
+    extra profiled step after the timed region;
   * `with_device_resize`: the same step starting from the ORIGINAL 640x640 uint8 images resident in HBM
     (bit-exact device PIL resize, pf_resize_batch_u8, inside the timed region);
   * `latency_ms`: batch-1 / batch-8 latency of the hot path (device resident) and of inference() / inference_batch()
     from host numpy images;
-  * `parity`: one image of the LAST timed step checked against the CPU oracle after the timed loop.
+  * `parity`: one image of the LAST timed step checked against the CPU oracle after the timed loop;
+  * the other precision, the other BASELINE configs, the host-edge stream and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned (float32 .npy, a seeded sample of the images, <= 64 MB)
+so that two builds can be compared output for output: the inputs are seeded, identical from run to run.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python bench.py --gpus N ...          (no WORLD_SIZE in the environment: re-launches itself as N ranks, one per GPU, under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --workload mixed ...  (BASELINE configs[4]: mixed-resolution stream, bucketed resize-in / post-process-out, per-bucket images/sec)
@@ -53,18 +60,25 @@ def parse(argv=None):
                     help="arithmetic of the dense contractions; fp32 (split-f16, fp32-class accuracy) is the parity mode and the headline; "
                          "fp32_bf16x6 = exact bf16 split (no range window); no reduced-precision mode is offered")
     ap.add_argument("--autotune", type=int, default=0, help="1: time every tile configuration for this batch size before the warm-up (default: shipped tile table)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also take every figure and check beyond the headline (events and roofline, parity against the CPU oracle, "
+                    "device resize, other precision, latency, other BASELINE configs, host-edge stream, CPU baseline); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32; params of every image, "
+                    "network-resolution and original-size fields of a fixed seeded sample of the images; <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--defer-params", type=int, default=1, help="1 (default): the ParamNet branch of step i runs on the engine's own stream next to step i + 1's backbone (pf_set_defer_params); "
                     "every step's work still completes inside the timed region (join + device synchronize before the clock stops)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the device-resize figure, the latency numbers and the parity check")
-    ap.add_argument("--events-in-timed", type=int, default=1, help="bracket the launches of >= 200 GFLOP (the dominant decoder convs) with HIP events inside the timed region (every timed step; "
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no events, no roofline figures")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the device-resize figure, the latency numbers and the parity check")
+    ap.add_argument("--events-in-timed", type=int, default=1, help="with --full: bracket the launches of >= 200 GFLOP (the dominant decoder convs) with HIP events inside the timed region (every timed step; "
                                                                    "negligible overhead) and take the per-class profile in one extra step after it; 0: no events at all")
     ap.add_argument("--workload", default="fixed", choices=("fixed", "mixed"),
                     help="fixed: BASELINE configs[2] (the headline: --batch images of --size x --size per GPU); mixed: configs[4], a stream of 384x512 / 640x640 / 1024x1365 "
                          "originals (1:2:1) resident in HBM, sharded round-robin within each (H, W) bucket, device resize + forward + post-process per step, per-bucket images/sec")
     ap.add_argument("--dry-run-cpu", action="store_true", help="control-flow test: stub engine on CPU, gloo backend (no GPU, no numbers)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def pmc_traffic():
@@ -150,6 +164,37 @@ def parity_check(version, resized_u8, hw, out, index):
         ok = ok and dpar <= 1e-4
     res["ok"] = bool(ok)
     return res
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, out, sizes, seed=0):
+    """--dump-outputs: the arrays the last timed step returned to its caller, as float32 DIR/<name>.npy.  `params` holds the ParamNet rows of every image (all ranks);
+    the dense outputs (network-resolution pred_gravity / pred_latitude, original-size up-vector / latitude fields) are kept whole for a fixed seeded sample of the
+    images that fits DUMP_LIMIT_BYTES.  Call it before anything else runs on the engine: its output buffers may be reused."""
+    pg, pl, fields, gathered = out
+    header = 256  # room for one .npy header
+    arrays = {}
+    used = 0
+    if gathered is not None:
+        arrays["params"] = gathered
+        used += 4 * gathered.numel() + header
+    chosen = []
+    for i in np.random.default_rng(seed).permutation(len(sizes)).tolist():
+        need = 4 * (pg[i].numel() + pl[i].numel() + fields[i][0].numel() + fields[i][1].numel()) + 4 * header
+        if used + need <= DUMP_LIMIT_BYTES:
+            chosen.append(i)
+            used += need
+    for i in sorted(chosen):
+        arrays[f"image{i:04d}_pred_gravity"] = pg[i]
+        arrays[f"image{i:04d}_pred_latitude"] = pl[i]
+        arrays[f"image{i:04d}_gravity_original"] = fields[i][0]
+        arrays[f"image{i:04d}_latitude_original"] = fields[i][1]
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+    return sorted(chosen)
 
 
 class _StubEngine:
@@ -324,10 +369,11 @@ def main(argv=None):
         step()
     drain((None, None, None, None))
     barrier()
-    # Per-launch HIP events INSIDE the timed region on the launches of >= 200 GFLOP only (the dominant decoder convs: ~6 per step), in every timed step: a dozen event
+    # --full: per-launch HIP events INSIDE the timed region on the launches of >= 200 GFLOP only (the dominant decoder convs: ~6 per step), in every timed step: a dozen event
     # records per step cost nothing, so `value` and `roofline` come from the same steps.  The per-class figures (all split GEMMs, depthwise, LayerNorm, attention) need an
     # event pair around each of the ~330 launches of a step (+15 % step time, one stream): they are taken in ONE EXTRA step after the timed region.
-    use_events = bool(args.events_in_timed) and not args.no_roofline
+    full = args.full
+    use_events = full and bool(args.events_in_timed) and not args.no_roofline
     if use_events:
         eng.profile_begin(classes=("igemm", "igemm_sb"), large_only=True)
     ev_steps = args.steps
@@ -338,11 +384,14 @@ def main(argv=None):
     out = drain(out)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, out, sizes)
+        print(f"bench.py: outputs of the last timed step written to {args.dump_outputs} (dense outputs of images {dumped})", file=sys.stderr)
     # Every step runs the same batch, so the scalars of a step whose ParamNet branch ran BESIDE the next step's backbone must equal, bit for bit, those of the last
     # step, whose branch ran alone after the join -- the parity check below only sees the last step (round 4: a packed-FMA operand form that was only wrong beside
     # other kernels went through exactly that gap, tests/test_gpu_e2e.py::test_deferred_paramnet_branch_equals_joined_forward caught it)
     deferred_identical = None
-    if defer and not dry and local.get("overlapped") is not None and local.get("last") is not None and args.steps >= 2:
+    if full and defer and not dry and local.get("overlapped") is not None and local.get("last") is not None and args.steps >= 2:
         deferred_identical = bool(torch.equal(local["overlapped"], local["last"]))
     if defer:
         spf.set_pipeline(False)  # everything after the timed region (extra profiled step, latency figures, parity check) reads its results right away
@@ -564,11 +613,12 @@ def main(argv=None):
             line["step_split_ms"] = {**{k: round(v, 3) for k, v in phases.items()}, "total": round(tot, 3),
                                      "share": {k: round(v / tot, 4) for k, v in phases.items()},
                                      "measured": "extra profiled step after the timed region (pf_profile_phases); includes launch gaps and the profile's own event pairs"}
-    line["host_resize_ms_per_image"] = round(1000.0 * t_resize, 3)
+    if full:
+        line["host_resize_ms_per_image"] = round(1000.0 * t_resize, 3)
     if deferred_identical is not None:
         line["deferred_branch_bit_identical"] = deferred_identical  # scalars of the step before the last (branch beside the last step's backbone) == the last step's (branch alone)
 
-    if not dry and not args.no_extras:
+    if full and not dry and not args.no_extras:
         # ---- (1) parity of the timed configuration: one image of the LAST timed step against the CPU oracle
         try:
             pi = min(Bl - 1, 3)
@@ -667,7 +717,7 @@ def main(argv=None):
             line["latency_ms"] = lat
         except Exception as e:
             line["latency_ms"] = {"error": repr(e)}
-    if not dry and not args.no_extras and world == 1 and not mixed:
+    if full and not dry and not args.no_extras and world == 1 and not mixed:
         # ---- (4) the host edge, one process: host numpy 640x640 images -> pinned staging -> H2D -> bit-exact device resize -> forward -> post-process -> pinned D2H of the
         #      four field tensors, through PerspectiveFields.inference_stream (three streams, deferred ParamNet branch); what a caller that starts from decoded images gets
         try:
@@ -726,7 +776,7 @@ def main(argv=None):
             del m1, e1
         except Exception as e:
             line["configs_1"] = {"error": repr(e)}
-    if not dry and not args.no_extras and world == 1 and not mixed:
+    if full and not dry and not args.no_extras and world == 1 and not mixed:
         # ---- (6) the DEFAULT-constructed model: PerspectiveFields(version) has precision="auto", which reads the saturation counter behind every forward (a 4-byte copy
         #      and a host synchronisation) and builds the reference's result dicts -- the headline drives the engine directly with the fast mode pinned.  Same device-resident
         #      batch through the engine path of inference_batch (PerspectiveFields._run: forward, counter read, post-process, dicts), forwards joined.
@@ -775,7 +825,7 @@ def main(argv=None):
             del orig_m, batch_m, img_m
         except Exception as e:
             line["configs_4"] = {"error": repr(e)}
-    if world == 1 and not args.no_cpu_baseline and not dry:
+    if full and world == 1 and not args.no_cpu_baseline and not dry:
         try:
             line["cpu_baseline"] = cpu_baseline(args.version, S)
         except Exception as e:  # the checker failing must not hide the measurement

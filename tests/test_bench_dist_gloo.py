@@ -83,3 +83,23 @@ def test_bench_mixed_workload_shards_by_bucket(world):
     assert sum(v["images_per_step_all_ranks"] for v in pb.values()) == n
     assert pb["640x640"]["images_per_step_all_ranks"] == sum(1 for i in range(n) if i % 4 in (1, 2))
     assert abs(d["value"] - n * 2 / (d["ms_per_step"] * 2e-3)) <= 0.02 * d["value"]
+
+
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs DIR: float32 .npy files of the last timed step, the ParamNet rows of every image, <= 64 MB, identical from run to run (seeded inputs)."""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run-cpu", "--steps", "2", "--warmup", "1", "--batch", "6", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len([ln for ln in r.stdout.splitlines() if ln.startswith("{")]) == 1
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert a.keys() == b.keys() and a["params.npy"].shape == (6, 8)
+    assert any(k.endswith("_gravity_original.npy") for k in a) and any(k.endswith("_pred_latitude.npy") for k in a)
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
