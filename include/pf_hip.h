@@ -253,6 +253,43 @@ int pf_postprocess_batch(pf_handle h, int batch, const float* d_pred_gravity, co
  * pred_latitude_original: d_up [2][H][W] unit vectors, d_lat [H][W] degrees.  No handle: the op is stateless. */
 int pf_fields_from_params(int device, const float* d_cam5, int H, int W, float* d_up, float* d_lat, void* stream);
 
+/* The inverse of pf_fields_from_params: perspective fields -> camera parameters, a batched per-image Levenberg-Marquardt
+ * least-squares fit.  Parameters theta = (roll, pitch, f, cx, cy): roll / pitch in radians, f = rel_focal,
+ * cx / cy = rel_cx / rel_cy.  free_pp = 0: 3 free parameters, cx / cy held at their start values (0 without d_init); 1: all 5 free.
+ * Model at pixel (row, col) of an H x W image, with px = col + 0.5, py = row + 0.5, F = f*H, Cx = (cx + 0.5)*W, Cy = (cy + 0.5)*H:
+ *   up  u = -(sin r cos p F + sin p (px - Cx), cos r cos p F + sin p (py - Cy)) / |.|   (the reference's (vvp - xy) sign(p) times
+ *       |sin p|: same direction for p != 0, the reference's (-sin r, -cos r) at p = 0, no 1/sin p)
+ *   lat = -atan2(y_w, sqrt(x_w^2 + z_w^2)) degrees on the reference's linspace grid x = (col W/(W-1) - Cx)/F, y = (row H/(H-1) - Cy)/F,
+ *       exactly as pf_fields_from_params.
+ * Residuals r_up = (u_model - u_pred) * 180/pi (2 components), r_lat = lat_model - lat_pred (degrees); pixels with a non-finite
+ * input value are skipped.  Loss sum w_up rho(|r_up|) + w_lat rho(|r_lat|), rho = r^2/2 (PF_FIT_LOSS_L2) or Huber with
+ * huber_delta_deg (PF_FIT_LOSS_HUBER, by IRLS weights).  Start: d_init = NULL -> roll / pitch from the fields at the image centre and
+ * f from a 16-candidate vFoV search in [15, 150] deg; else d_init = DEVICE [B][5] theta (the layout of d_cam5).
+ * Stops per image when an accepted step changes the cost by < 1e-10 relative, a step is < 1e-9, or after max_iter steps.
+ * h_hw = HOST [B][2] (H, W), each >= 8; h_up / h_lat = HOST arrays of B DEVICE pointers ([2][H][W] and [H][W] degrees fp32).
+ * d_out = DEVICE [B][PF_FIT_COLS] fp32, columns below (angles in degrees).  Workspace: pf_fit_camera_workspace_bytes(B, h_hw).
+ * Enqueues max_iter + 1 (accumulate, solve) launch pairs per 32 images on `stream`, no host synchronisation; deterministic. */
+#define PF_FIT_COL_ROLL 0
+#define PF_FIT_COL_PITCH 1
+#define PF_FIT_COL_VFOV 2          /* 2 atan(1 / (2 f)) */
+#define PF_FIT_COL_REL_FOCAL 3
+#define PF_FIT_COL_GENERAL_VFOV 4  /* acos((P + Q - 1) / (2 sqrt(P Q))), P = f^2 + cx^2 + (cy + 1/2)^2, Q = f^2 + cx^2 + (cy - 1/2)^2 */
+#define PF_FIT_COL_REL_CX 5
+#define PF_FIT_COL_REL_CY 6
+#define PF_FIT_COL_RMS_UP 7        /* sqrt(mean |r_up|^2), degree scale */
+#define PF_FIT_COL_RMS_LAT 8       /* sqrt(mean r_lat^2), degrees */
+#define PF_FIT_COL_COST 9          /* the loss above at the result */
+#define PF_FIT_COL_ITERATIONS 10   /* LM steps evaluated (accepted or rejected) */
+#define PF_FIT_COL_CONVERGED 11    /* 1: a tolerance was met; 0: stopped at max_iter */
+#define PF_FIT_COL_VALID_PIXELS 12 /* pixels with finite input */
+#define PF_FIT_COLS 13
+#define PF_FIT_LOSS_L2 0
+#define PF_FIT_LOSS_HUBER 1
+size_t pf_fit_camera_workspace_bytes(int batch, const int32_t* h_hw);
+int pf_fit_camera(int device, int batch, const int32_t* h_hw, const float* const* h_up, const float* const* h_lat, const float* d_init,
+                  int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* d_workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* ---- kernel-level entry points (used by the parity tests; same kernels pf_forward runs) ----
  * NHWC fp32 device activations; weights are HOST pointers in the reference's layouts.
  * "planes": the engine's internal split activation formats -- an fp32 tensor stored as planes of 16-bit values, plane k at

@@ -1981,6 +1981,70 @@ int pf_fields_from_params(int device, const float* d_cam5, int H, int W, float* 
   return PF_OK;
 }
 
+// workspace of pf_fit_camera: per-image LM state, then every image's partial records, each region 256-byte aligned
+static size_t fit_state_bytes(int B) { return ((size_t)B * FIT_STATE * sizeof(double) + 255) & ~(size_t)255; }
+static size_t fit_part_bytes(int H, int W) { return ((size_t)fit_blocks_per_image(H, W) * FIT_REC * sizeof(double) + 255) & ~(size_t)255; }
+
+size_t pf_fit_camera_workspace_bytes(int B, const int32_t* hw) {
+  if (B <= 0 || !hw) return 0;
+  size_t n = 256 + fit_state_bytes(B);  // + 256: alignment of the caller's pointer
+  for (int i = 0; i < B; ++i) {
+    if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) return 0;
+    n += fit_part_bytes(hw[2 * i], hw[2 * i + 1]);
+  }
+  return n;
+}
+
+int pf_fit_camera(int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int loss,
+                  float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes, void* stream) {
+  std::string err;
+  int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  if (B <= 0 || !hw || !up || !lat || !d_out) { g_create_error = "pf_fit_camera: bad argument"; return PF_ERR_ARG; }
+  if ((free_pp != 0 && free_pp != 1) || (loss != PF_FIT_LOSS_L2 && loss != PF_FIT_LOSS_HUBER) || max_iter < 1 || max_iter > 1000) {
+    g_create_error = fmt("pf_fit_camera: bad option (free_pp %d, loss %d, max_iter %d)", free_pp, loss, max_iter);
+    return PF_ERR_ARG;
+  }
+  if (!(w_up >= 0.f && w_lat >= 0.f && std::isfinite(w_up) && std::isfinite(w_lat) && w_up + w_lat > 0.f) ||
+      (loss == PF_FIT_LOSS_HUBER && !(huber_delta_deg > 0.f && std::isfinite(huber_delta_deg)))) {
+    g_create_error = "pf_fit_camera: weights must be finite, >= 0 and not both 0; huber_delta_deg must be finite and > 0";
+    return PF_ERR_ARG;
+  }
+  for (int i = 0; i < B; ++i) {
+    if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) { g_create_error = fmt("pf_fit_camera: image %d is %d x %d, smaller than 8 x 8", i, hw[2 * i], hw[2 * i + 1]); return PF_ERR_ARG; }
+    if (!up[i] || !lat[i]) { g_create_error = fmt("pf_fit_camera: NULL field pointer of image %d", i); return PF_ERR_ARG; }
+  }
+  const size_t need = pf_fit_camera_workspace_bytes(B, hw);
+  if (!ws || ws_bytes < need) { g_create_error = fmt("pf_fit_camera: needs %zu workspace bytes, got %zu", need, ws_bytes); return PF_ERR_WORKSPACE; }
+  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+  double* state = reinterpret_cast<double*>(base);
+  char* part = base + fit_state_bytes(B);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat};
+  std::vector<FitBatch> groups;
+  for (int i0 = 0; i0 < B; i0 += FitBatch::MAX) {
+    FitBatch fb;
+    fb.n = std::min(B - i0, (int)FitBatch::MAX);
+    for (int k = 0; k < fb.n; ++k) {
+      const int i = i0 + k, H = hw[2 * i], W = hw[2 * i + 1];
+      fb.H[k] = H; fb.W[k] = W; fb.nblk[k] = fit_blocks_per_image(H, W);
+      fb.up[k] = up[i]; fb.lat[k] = lat[i];
+      fb.part[k] = reinterpret_cast<double*>(part);
+      part += fit_part_bytes(H, W);
+    }
+    fb.state = state + (size_t)i0 * FIT_STATE;
+    fb.out = d_out + (size_t)i0 * PF_FIT_COLS;
+    fb.init = d_init ? d_init + (size_t)i0 * 5 : nullptr;
+    groups.push_back(fb);
+  }
+  // no host synchronisation: every image stops on its own flag, the launches run out as no-ops
+  for (const FitBatch& fb : groups) launch_fit_init(fb, prm, s);
+  for (int it = 0; it <= max_iter; ++it)
+    for (const FitBatch& fb : groups) launch_fit_iteration(fb, prm, s);
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_fit_camera: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
 int pf_profile_begin(pf_handle h, unsigned class_mask) {
   if (!h) return PF_ERR_ARG;
   h->prof.reset();

@@ -363,4 +363,27 @@ void launch_fields_from_params(const float* cam5, int H, int W, float* up, float
 // ParamNet scalar formulas (param_network.py:62-67): raw [B][nraw] -> [B][8] (layout: include/pf_hip.h)
 void launch_paramnet_scalars(const float* raw, int nraw, float* out8, int B, int mode, hipStream_t s);
 
+// perspective fields -> camera parameters (fit_camera.hip, include/pf_hip.h pf_fit_camera): up to FitBatch::MAX images per
+// launch, per-image sizes and pointers in the kernel arguments
+constexpr int FIT_STATE = 40;  // doubles of per-image LM state
+constexpr int FIT_REC = 24;    // doubles of one accumulate block's partial record
+struct FitParams {
+  int free_pp, loss;
+  float huber_delta, w_up, w_lat;
+};
+struct FitBatch {
+  static constexpr int MAX = 32;
+  int n;
+  int H[MAX], W[MAX], nblk[MAX];
+  const float* up[MAX];   // [2][H][W]
+  const float* lat[MAX];  // [H][W] degrees
+  double* part[MAX];      // [nblk][FIT_REC]
+  double* state;          // [n][FIT_STATE]
+  float* out;             // [n][PF_FIT_COLS]
+  const float* init;      // NULL or [n][5]
+};
+int fit_blocks_per_image(int H, int W);
+void launch_fit_init(const FitBatch& fb, const FitParams& prm, hipStream_t s);
+void launch_fit_iteration(const FitBatch& fb, const FitParams& prm, hipStream_t s);  // one accumulate + solve pair
+
 }  // namespace pf

@@ -15,6 +15,7 @@ device raises.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from collections import OrderedDict
 from typing import Dict, List, Optional, Union
@@ -444,6 +445,22 @@ class PerspectiveFields(nn.Module):
         return fields_from_params(pred["pred_roll"], pred["pred_pitch"], pred["pred_rel_focal"], pred["pred_rel_cx"], pred["pred_rel_cy"],
                                   height, width, mode="deg")
 
+    def fit_camera(self, preds, **kw):
+        """Camera parameters fitted to the dense fields of one inference() result (a dict) or of an inference_batch() list, on the
+        GPU (see fit_camera_params for the options and the returned entries).  Works on every zoo version, PersNet included.
+        init="paramnet" starts from the result's own ParamNet scalars (ParamNet models only).  Returns new dicts; the
+        inference results are not changed."""
+        single = isinstance(preds, dict)
+        plist = [preds] if single else list(preds)
+        if isinstance(kw.get("init"), str):
+            if kw["init"] != "paramnet":
+                raise ValueError("init must be None, 'paramnet' or a list of parameter dicts")
+            if not self.param_on:
+                raise PfError(f"'{self.version}' has no ParamNet: init='paramnet' needs pred_* scalars")
+            kw["init"] = plist
+        res = fit_camera_params([p["pred_gravity_original"] for p in plist], [p["pred_latitude_original"] for p in plist], **kw)
+        return res[0] if single else res
+
     def forward(self, batched_inputs) -> List[dict]:
         """batched_inputs: list of {"image": (3,320,320) float BGR 0..255, "height", "width"} (reference :223-272)."""
         with torch.no_grad():
@@ -632,3 +649,84 @@ def general_vfov_to_focal(rel_cx, rel_cy, gvfov_deg):
     u = np.where(c >= 0, (1.0 + disc), (1.0 - disc)) / (2.0 * s2)
     f2 = u - cy * cy - 0.25 - cx * cx
     return np.sqrt(np.abs(f2))
+
+
+# columns of the pf_fit_camera output row (include/pf_hip.h PF_FIT_COL_*)
+_FIT_COLS = ("pred_roll", "pred_pitch", "pred_vfov", "pred_rel_focal", "pred_general_vfov", "pred_rel_cx", "pred_rel_cy",
+             "fit_rms_up_deg", "fit_rms_lat_deg", "fit_cost", "fit_iterations", "fit_converged", "fit_valid_pixels")
+_FIT_LOSSES = {"l2": 0, "huber": 1}
+
+
+def fit_camera_params(up, lat, *, free_principal_point=False, loss="l2", huber_delta_deg=2.0, weights=(1.0, 1.0), max_iter=20, init=None):
+    """Perspective fields -> camera parameters on the GPU: the inverse of `fields_from_params`, a per-image Levenberg-Marquardt
+    least-squares fit of its model to an up field (2,H,W) and a latitude map (H,W) in degrees (the layout of
+    `pred_gravity_original` / `pred_latitude_original`).  Model, loss and stopping rule: include/pf_hip.h pf_fit_camera.
+
+    up / lat: one pair of device tensors, or lists of pairs (sizes may differ; one launch sequence per 32 images).
+    free_principal_point: fit rel_cx / rel_cy too (5 parameters); otherwise they stay at their start values (0 without `init`).
+    loss: "l2" or "huber" (threshold huber_delta_deg); weights = (w_up, w_lat); max_iter: LM steps per image.
+    init: optional start, one dict (or a list of dicts) with pred_roll, pred_pitch (degrees), pred_rel_focal and optionally
+    pred_rel_cx / pred_rel_cy -- e.g. an inference() result of a ParamNet model.
+
+    Returns one dict per image (a single dict for a single pair): pred_roll, pred_pitch, pred_vfov, pred_rel_focal,
+    pred_general_vfov, pred_rel_cx, pred_rel_cy (angles in degrees), fit_rms_up_deg, fit_rms_lat_deg, fit_cost, fit_iterations,
+    fit_converged, fit_valid_pixels -- 0-d device tensors (no host synchronisation), so `fields_from_params` can take the
+    pred_* entries directly.  GPU only: CPU tensors raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    single = torch.is_tensor(up)
+    ups, lats = ([up], [lat]) if single else (list(up), list(lat))
+    if len(ups) != len(lats) or not ups:
+        raise ValueError("fit_camera_params needs as many latitude maps as up fields, at least one")
+    if loss not in _FIT_LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_FIT_LOSSES)}")
+    for u, l in zip(ups, lats):
+        if not (torch.is_tensor(u) and torch.is_tensor(l)):
+            raise TypeError("fit_camera_params takes torch tensors")
+        if not (u.is_cuda and l.is_cuda):
+            raise PfError("fit_camera_params runs on the GPU only (no CPU path)")
+        if u.dim() != 3 or u.shape[0] != 2 or tuple(l.shape) != tuple(u.shape[1:]):
+            raise ValueError(f"up must be (2, H, W) and lat (H, W); got {tuple(u.shape)} and {tuple(l.shape)}")
+    dev = ups[0].device
+    if any(t.device != dev for t in ups + lats):
+        raise ValueError("fit_camera_params: all fields must be on one device")
+    ups = [u.to(torch.float32).contiguous() for u in ups]
+    lats = [l.to(torch.float32).contiguous() for l in lats]
+    B = len(ups)
+    d_init = None
+    if init is not None:
+        inits = [init] if isinstance(init, dict) else list(init)
+        if len(inits) != B:
+            raise ValueError(f"init has {len(inits)} entries for {B} images")
+        rows = []
+        for d in inits:
+            z = torch.zeros((), dtype=torch.float64, device=dev)
+            v = [torch.as_tensor(d[k], dtype=torch.float64).to(dev).reshape(()) for k in ("pred_roll", "pred_pitch", "pred_rel_focal")]
+            v += [torch.as_tensor(d[k], dtype=torch.float64).to(dev).reshape(()) if k in d else z for k in ("pred_rel_cx", "pred_rel_cy")]
+            v[0], v[1] = torch.deg2rad(v[0]), torch.deg2rad(v[1])
+            rows.append(torch.stack(v))
+        d_init = torch.stack(rows).to(torch.float32).contiguous()
+    hw = (ctypes.c_int32 * (2 * B))(*[s for u in ups for s in (int(u.shape[1]), int(u.shape[2]))])
+    p_up = (ctypes.c_void_p * B)(*[u.data_ptr() for u in ups])
+    p_lat = (ctypes.c_void_p * B)(*[l.data_ptr() for l in lats])
+    lib = load_library()
+    ws_n = int(lib.pf_fit_camera_workspace_bytes(B, hw))
+    if ws_n == 0:
+        small = [tuple(u.shape[1:]) for u in ups if min(u.shape[1:]) < 8]
+        raise PfError(f"fit_camera_params: images must be at least 8 x 8 (got {small})")
+    ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
+    out = torch.empty((B, len(_FIT_COLS)), dtype=torch.float32, device=dev)
+    w_up, w_lat = (float(w) for w in weights)
+    with torch.cuda.device(dev):
+        _check(lib.pf_fit_camera(dev.index, B, hw, p_up, p_lat, d_init.data_ptr() if d_init is not None else None, int(bool(free_principal_point)),
+                                 _FIT_LOSSES[loss], float(huber_delta_deg), w_up, w_lat, int(max_iter), out.data_ptr(), ws.data_ptr(), ws_n,
+                                 _stream_ptr()), None, "pf_fit_camera")
+    iters = out[:, 10].to(torch.int32)
+    conv = out[:, 11] != 0
+    valid = out[:, 12].to(torch.int64)
+    res = []
+    for i in range(B):
+        d = {k: out[i, j] for j, k in enumerate(_FIT_COLS[:10])}
+        d["fit_iterations"], d["fit_converged"], d["fit_valid_pixels"] = iters[i], conv[i], valid[i]
+        res.append(d)
+    return res[0] if single else res
