@@ -290,6 +290,37 @@ int pf_fit_camera(int device, int batch, const int32_t* h_hw, const float* const
                   int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* d_workspace,
                   size_t workspace_bytes, void* stream);
 
+/* Equirectangular panoramas -> camera views and their ground-truth perspective fields on the device: the reference's labelled-data
+ * tooling, PanoCam.get_image / crop_equi (utils/panocam.py:132-249), crop_distortion (:558-752, Unified Spherical Model) and
+ * get_up_general / get_lat_general (:451-556).  DESIGN.md section 11.
+ * Per crop theta = d_cam7 row = {roll r, pitch p, yaw psi (RADIANS), rel_focal f, rel_cx cx, rel_cy cy, xi}, DEVICE [batch][7]; xi = 0: pinhole.
+ * Every crop is H x W (>= 1 each).  Model:
+ *   intrinsics  F = f*H, Cx = (cx + 1/2)*W, Cy = (cy + 1/2)*H; image point (a, b) -> x = (a - Cx)/F, y = (b - Cy)/F
+ *   ray         rho^2 = x^2 + y^2, disc = 1 + (1 - xi^2) rho^2, eta = (xi + sqrt(disc)) / (1 + rho^2), X = (eta x, eta y, eta - xi), |X| = 1;
+ *               disc < 0 (only for xi > 1): the pixel has no ray
+ *   world       X_w = R X, R = R_pitch(p) R_roll(r), R_roll = [[cos r, -sin r, 0], [sin r, cos r, 0], [0, 0, 1]],
+ *               R_pitch = [[1, 0, 0], [0, cos p, -sin p], [0, sin p, cos p]] (pf_fields_from_params' rotation: x right, y down, z forward,
+ *               world up = (0, -1, 0), positive pitch looks up)
+ *   sphere      lat = -atan2(X_w.y, hypot(X_w.x, X_w.z)), lon = yaw + atan2(X_w.x, X_w.z) wrapped into [-pi, pi) (positive yaw turns the view
+ *               towards higher panorama columns)
+ *   panorama    Hp x Wp (each >= 2), pixel centres at integers: u = (lon/2pi + 1/2) Wp - 1/2, v = (1/2 - lat/pi) Hp - 1/2 (row 0 = north,
+ *               lon = 0 at the centre column); bilinear, columns wrap modulo Wp, rows clamp to [0, Hp - 1]
+ *   image       sampled at (a, b) = (col + 1/2, row + 1/2); PF_PANO_U8: the fp32 value rounded half up, clamped to [0, 255]; PF_PANO_F32: the
+ *               value; no ray: 0
+ *   labels      (layout of pred_gravity_original / pred_latitude_original; yaw does not enter; no ray: NaN)
+ *               xi = 0: bit-identical to pf_fields_from_params with the same (r, p, f, cx, cy)
+ *               otherwise up at (col + 1/2, row + 1/2): g = R^T (0, -1, 0), D = X_z + xi, s = g_z + xi (X . g),
+ *               up ~ (g_x D - X_x s, g_y D - X_y s) normalised; lat in degrees at the linspace point (col W/(W-1), row H/(H-1)) (0 for a size of 1)
+ * h_pano = HOST array of n_pano DEVICE pointers, (Hp, Wp, 3) channel-interleaved, all of type `dtype`; h_pano_hw = HOST [n_pano][2] (Hp, Wp);
+ * h_pano_index = HOST [batch], the panorama of each crop.  d_img = DEVICE [batch][H][W][3] of `dtype` (required); d_up [batch][2][H][W] and
+ * d_lat [batch][H][W] fp32: both or neither (NULL: no labels).  Argument errors return PF_ERR_ARG before any device work.
+ * One launch per 32 crops on `stream`, no host synchronisation; stateless, no handle; deterministic, each crop's bits independent of the batch. */
+#define PF_PANO_U8 0
+#define PF_PANO_F32 1
+int pf_pano_crop(int device, int n_pano, const void* const* h_pano, const int32_t* h_pano_hw /*[n_pano][2]*/, int dtype, int batch,
+                 const int32_t* h_pano_index /*[batch]*/, const float* d_cam7 /*[batch][7]*/, int H, int W,
+                 void* d_img /*[batch][H][W][3], dtype*/, float* d_up /*[batch][2][H][W]*/, float* d_lat /*[batch][H][W]*/, void* stream);
+
 /* ---- kernel-level entry points (used by the parity tests; same kernels pf_forward runs) ----
  * NHWC fp32 device activations; weights are HOST pointers in the reference's layouts.
  * "planes": the engine's internal split activation formats -- an fp32 tensor stored as planes of 16-bit values, plane k at

@@ -1981,6 +1981,51 @@ int pf_fields_from_params(int device, const float* d_cam5, int H, int W, float* 
   return PF_OK;
 }
 
+int pf_pano_crop(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
+                 const float* d_cam7, int H, int W, void* d_img, float* d_up, float* d_lat, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_pano_crop: " + m; return PF_ERR_ARG; };
+  if (n_pano < 1 || !pano || !pano_hw) return bad("needs at least one panorama (h_pano, h_pano_hw)");
+  if (dtype != PF_PANO_U8 && dtype != PF_PANO_F32) return bad(fmt("unknown dtype %d", dtype));
+  for (int k = 0; k < n_pano; ++k) {
+    if (!pano[k]) return bad(fmt("NULL pointer of panorama %d", k));
+    if (pano_hw[2 * k] < 2 || pano_hw[2 * k + 1] < 2) return bad(fmt("panorama %d is %d x %d, smaller than 2 x 2", k, pano_hw[2 * k], pano_hw[2 * k + 1]));
+  }
+  if (B < 1 || !pano_index || !d_cam7 || !d_img) return bad("batch >= 1, h_pano_index, d_cam7 and d_img are required");
+  if (H < 1 || W < 1) return bad(fmt("output size %d x %d", H, W));
+  if (!d_up != !d_lat) return bad("d_up and d_lat are both given or both NULL");
+  for (int i = 0; i < B; ++i)
+    if (pano_index[i] < 0 || pano_index[i] >= n_pano) return bad(fmt("crop %d: panorama index %d of %d", i, pano_index[i], n_pano));
+  const int tpr = 16;  // a 64 x 16 pixel tile
+  const long tiles_x = (W + 4 * tpr - 1) / (4 * tpr), tiles_y = (H + 256 / tpr - 1) / (256 / tpr);
+  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("output size %d x %d too large", H, W));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  const size_t esz = dtype == PF_PANO_U8 ? 1 : 4, npx = (size_t)H * W;
+  const uintptr_t align = (reinterpret_cast<uintptr_t>(d_img) & (dtype == PF_PANO_U8 ? 3 : 15)) | (reinterpret_cast<uintptr_t>(d_up) & 15) |
+                          (reinterpret_cast<uintptr_t>(d_lat) & 15);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i0 = 0; i0 < B; i0 += PanoBatch::MAX) {
+    PanoBatch pb;
+    pb.n = std::min(B - i0, (int)PanoBatch::MAX);
+    pb.H = H; pb.W = W;
+    pb.tpr = tpr; pb.tiles_x = (int)tiles_x; pb.tiles_y = (int)tiles_y;
+    pb.vec = (W % 4 == 0 && align == 0) ? 1 : 0;
+    for (int k = 0; k < pb.n; ++k) {
+      const int p = pano_index[i0 + k];
+      pb.pano[k] = pano[p];
+      pb.Hp[k] = pano_hw[2 * p]; pb.Wp[k] = pano_hw[2 * p + 1];
+    }
+    pb.cam = d_cam7 + (size_t)i0 * 7;
+    pb.img = static_cast<char*>(d_img) + (size_t)i0 * npx * 3 * esz;
+    pb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
+    pb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
+    launch_pano_crop(pb, dtype, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_pano_crop: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
 // workspace of pf_fit_camera: per-image LM state, then every image's partial records, each region 256-byte aligned
 static size_t fit_state_bytes(int B) { return ((size_t)B * FIT_STATE * sizeof(double) + 255) & ~(size_t)255; }
 static size_t fit_part_bytes(int H, int W) { return ((size_t)fit_blocks_per_image(H, W) * FIT_REC * sizeof(double) + 255) & ~(size_t)255; }

@@ -386,4 +386,20 @@ int fit_blocks_per_image(int H, int W);
 void launch_fit_init(const FitBatch& fb, const FitParams& prm, hipStream_t s);
 void launch_fit_iteration(const FitBatch& fb, const FitParams& prm, hipStream_t s);  // one accumulate + solve pair
 
+// equirectangular panorama -> camera views + ground-truth fields (pano_crop.hip, include/pf_hip.h pf_pano_crop): up to
+// PanoBatch::MAX crops of one output size per launch, per-crop panorama pointers and sizes in the kernel arguments
+struct PanoBatch {
+  static constexpr int MAX = 32;
+  int n, H, W;
+  int tpr, tiles_x, tiles_y;  // threads per tile row (the tile is 4 tpr x 256 / tpr pixels), tiles per crop
+  int vec;                    // 1: W % 4 == 0 and 16-byte aligned outputs (4-byte for a uint8 image): vector stores
+  const void* pano[MAX];      // (Hp, Wp, 3) uint8 or fp32
+  int Hp[MAX], Wp[MAX];
+  const float* cam;  // [n][7]: roll, pitch, yaw (radians), rel_focal, rel_cx, rel_cy, xi
+  void* img;         // [n][H][W][3], the panorama's type
+  float* up;         // NULL (no labels) or [n][2][H][W]
+  float* lat;        // NULL or [n][H][W] degrees
+};
+void launch_pano_crop(const PanoBatch& pb, int dtype, hipStream_t s);
+
 }  // namespace pf

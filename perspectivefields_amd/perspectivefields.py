@@ -16,6 +16,7 @@ device raises.
 from __future__ import annotations
 
 import ctypes
+import operator
 import os
 from collections import OrderedDict
 from typing import Dict, List, Optional, Union
@@ -213,7 +214,10 @@ class PerspectiveFields(nn.Module):
         return results, params
 
     def _prepare_batch(self, img_bgr_list: List[np.ndarray]):
-        """host images -> (network input on the device, [(H, W)]): uint8 (B,320,320,3) through PIL (or the bit-identical device resize), float (B,3,320,320) otherwise"""
+        """host images -> (network input on the device, [(H, W)]): uint8 (B,320,320,3) through PIL (or the bit-identical device resize), float (B,3,320,320) otherwise.
+        A list of CUDA uint8 (H, W, 3) tensors on the model's device is resized on the device by the same bit-exact kernel whatever device_resize says."""
+        if any(torch.is_tensor(im) for im in img_bgr_list):
+            return self._prepare_device_batch(img_bgr_list)
         if any(im.dtype != np.uint8 for im in img_bgr_list):
             sizes, chw = [], []
             for img_bgr in img_bgr_list:
@@ -241,6 +245,23 @@ class PerspectiveFields(nn.Module):
             eng.resize_batch_into(views, batch)
         else:
             batch = torch.from_numpy(np.stack(resized)).to(self.device, non_blocking=False)  # uint8 (B,320,320,3)
+        return batch, sizes
+
+    def _prepare_device_batch(self, imgs):
+        if not all(torch.is_tensor(im) for im in imgs):
+            raise TypeError("inference_batch: a list mixes numpy arrays and tensors")
+        for im in imgs:
+            if im.dtype != torch.uint8:
+                raise TypeError(f"inference_batch takes uint8 device tensors only (got {im.dtype}); float images go through numpy")
+            if im.device != self.device:
+                raise ValueError(f"inference_batch: a tensor is on '{im.device}', the model on '{self.device}'")
+            if im.dim() != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+                raise ValueError(f"inference_batch: images must be (H, W, 3); got {tuple(im.shape)}")
+        eng = self._get_engine()
+        views = [(im.flip(-1) if self.input_format == "RGB" else im).contiguous() for im in imgs]   # the numpy path's channel flip
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+        batch = torch.empty((len(views), NET_H, NET_W, 3), dtype=torch.uint8, device=self.device)
+        eng.resize_batch_into(views, batch)
         return batch, sizes
 
     # ------------------------------------------------------------------ debug forward (sanitizer / shadow-compare mode)
@@ -730,3 +751,91 @@ def fit_camera_params(up, lat, *, free_principal_point=False, loss="l2", huber_d
         d["fit_iterations"], d["fit_converged"], d["fit_valid_pixels"] = iters[i], conv[i], valid[i]
         res.append(d)
     return res[0] if single else res
+
+
+# panorama element types of pf_pano_crop (include/pf_hip.h PF_PANO_*)
+PANO_U8, PANO_F32 = 0, 1
+_PANO_DTYPES = {torch.uint8: PANO_U8, torch.float32: PANO_F32}
+
+
+def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0.0, xi=0.0, height, width, pano_index=None, mode="deg", fields=True):
+    """Equirectangular panoramas -> camera views and their ground-truth perspective fields on the GPU: the reference's labelled-data
+    tooling (PanoCam.get_image / crop_equi, crop_distortion for the Unified Spherical Model, get_up_general / get_lat_general in
+    utils/panocam.py).  Camera model, sampling and labels: include/pf_hip.h pf_pano_crop.
+
+    pano: a CUDA tensor (Hp, Wp, 3), uint8 or float32, or a list of them (one dtype, one device).
+    roll, pitch, yaw (degrees unless mode="rad"), rel_focal, rel_cx, rel_cy, xi (0: pinhole; > 0: Unified Spherical Model): numbers,
+    0-d tensors or 1-d tensors / sequences, broadcast to the batch size B (1 when all are scalars); device tensors stay on the device.
+    pano_index: None (every crop from panorama 0) or B integers.  height, width: the size of every crop.
+    Returns (images (B, H, W, 3) in the panorama's dtype, up (B, 2, H, W), lat (B, H, W) degrees); up / lat are None with fields=False.
+    The labels use the layout of pred_gravity_original / pred_latitude_original; at xi = 0 they are bit-identical to
+    `fields_from_params` with the same arguments.  Pixels without a ray (xi > 1) are 0 in the image and NaN in the labels.
+
+    The orientation conventions are those of `fields_from_params` (pinned to the reference by tests/golden): x right, y down,
+    positive pitch looks up, positive yaw turns towards higher panorama columns, row 0 of the panorama is the north pole and its
+    centre column is longitude 0.  Pixel parity with the reference's equilib backend is not checked.  The reference's
+    get_image(vfov, im_w, im_h, azimuth, elevation, roll, ar) maps to height=im_h, width=im_w, yaw=azimuth, pitch=elevation, roll=roll,
+    rel_focal = 0.5 / tan(vfov / 2) (a centred crop with square pixels), rel_cx = rel_cy = 0, xi = 0.
+    GPU only: CPU panoramas raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    panos = [pano] if torch.is_tensor(pano) else list(pano)
+    if not panos:
+        raise ValueError("crop_panorama needs at least one panorama")
+    if not all(torch.is_tensor(p) for p in panos):
+        raise TypeError("crop_panorama takes torch tensors as panoramas")
+    if not all(p.is_cuda for p in panos):
+        raise PfError("crop_panorama runs on the GPU only (no CPU path)")
+    for p in panos:
+        if p.dim() != 3 or p.shape[2] != 3 or p.shape[0] < 2 or p.shape[1] < 2:
+            raise ValueError(f"a panorama must be (Hp, Wp, 3) with Hp, Wp >= 2; got {tuple(p.shape)}")
+        if p.dtype not in _PANO_DTYPES:
+            raise ValueError(f"panoramas must be uint8 or float32; got {p.dtype}")
+    if len({p.dtype for p in panos}) != 1 or len({p.device for p in panos}) != 1:
+        raise ValueError("crop_panorama: all panoramas must have one dtype and one device")
+    H, W = int(height), int(width)
+    if H < 1 or W < 1:
+        raise ValueError(f"crop size must be at least 1 x 1; got {H} x {W}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    dev = panos[0].device
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    ts = []   # validated where they are; moved to the device after every check
+    for name, v in (("roll", roll), ("pitch", pitch), ("yaw", yaw), ("rel_focal", rel_focal), ("rel_cx", rel_cx), ("rel_cy", rel_cy), ("xi", xi)):
+        t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float64))
+        if t.dim() > 1:
+            raise ValueError(f"{name} must be a number or a 1-d sequence; got shape {tuple(t.shape)}")
+        ts.append(t)
+    try:
+        shape = torch.broadcast_shapes(*[tuple(t.shape) for t in ts])
+    except RuntimeError as e:
+        raise ValueError(f"crop_panorama: camera parameters do not broadcast: {e}") from None
+    B = int(shape[0]) if shape else 1
+    if B < 1:
+        raise ValueError("crop_panorama needs at least one crop")
+    if pano_index is None:
+        idx = [0] * B
+    else:
+        idx = [operator.index(i) for i in (pano_index.tolist() if torch.is_tensor(pano_index) else pano_index)]
+        if len(idx) != B:
+            raise ValueError(f"pano_index has {len(idx)} entries for {B} crops")
+        if any(i < 0 or i >= len(panos) for i in idx):
+            raise ValueError(f"pano_index entries must be in [0, {len(panos)})")
+    ts = [t.to(device=dev, dtype=torch.float64) for t in ts]   # as fields_from_params: degrees -> radians in fp64, then fp32
+    if mode == "deg":
+        ts[0], ts[1], ts[2] = torch.deg2rad(ts[0]), torch.deg2rad(ts[1]), torch.deg2rad(ts[2])
+    cam = torch.stack([t.expand(B) for t in ts], 1).to(torch.float32).contiguous()
+    panos = [p.contiguous() for p in panos]
+    img = torch.empty((B, H, W, 3), dtype=panos[0].dtype, device=dev)
+    up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if fields else None
+    lat = torch.empty((B, H, W), dtype=torch.float32, device=dev) if fields else None
+    n = len(panos)
+    p_pano = (ctypes.c_void_p * n)(*[p.data_ptr() for p in panos])
+    hw = (ctypes.c_int32 * (2 * n))(*[s for p in panos for s in (int(p.shape[0]), int(p.shape[1]))])
+    c_idx = (ctypes.c_int32 * B)(*idx)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_pano_crop(dev.index, n, p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, cam.data_ptr(), H, W, img.data_ptr(),
+                                up.data_ptr() if fields else None, lat.data_ptr() if fields else None, _stream_ptr()), None, "pf_pano_crop")
+    return img, up, lat
