@@ -240,6 +240,31 @@ int pf_debug_forward_u8(pf_handle h, int batch, const uint8_t* d_in_u8, float* d
 int pf_debug_taps(pf_handle h, int max_records, char* names /*[max][64]*/, long long* byte_offsets, int* shapes /*[max][4]: B, H, W, C*/);
 int pf_debug_ranges(pf_handle h, int max_records, char* names /*[max][96]*/, long long* elems, float* stats /*[max][4]*/);
 
+/* ---- Dispatch report: WHICH kernels the last pf_forward_* of this handle launched, on how many streams, out of how much scratch.  That is decided per forward from the
+ * batch size and the PF_* switches; the report lets a caller (and the test-suite) see the decision instead of trusting it.  Plain host counters incremented at the
+ * decision points: no device work, no synchronisation, the launches are the same with or without a reader.  out = HOST array of at least PF_DISPATCH_COLS entries.
+ * A graph REPLAY (pf_forward_u8_graph after its capture) runs no host dispatch and leaves the report of the capturing call; pf_autotune's forward reports only the
+ * peaks and the launcher counts.  With PF_DEFER_AT > 0 the previous forward's ParamNet branch is issued, and counted, inside the next forward. */
+#define PF_DISPATCH_BATCH 0
+#define PF_DISPATCH_S3_SPLIT_TAKEN 1          /* 1: MiT stage 3 walked the batch as two half-batches on two streams */
+#define PF_DISPATCH_RB_LAUNCHES 2             /* row-block linears (rb_gemm.hip) and rb_chain.hip launches */
+#define PF_DISPATCH_SPLITK_LAUNCHES 3         /* convs that really ran split-K (+ reduce) */
+#define PF_DISPATCH_SPLITK_MAX_FACTOR 4       /* ... and their largest factor (0: none) */
+#define PF_DISPATCH_WINO_LAUNCHES 5           /* Winograd F(2x2, 3x3) launches */
+#define PF_DISPATCH_WINO_HALF_LAUNCHES 6      /* ... of them in the half-patch geometry */
+#define PF_DISPATCH_THIN128_LAUNCHES 7        /* thin 128 -> 128 projections (thin_linear.hip) */
+#define PF_DISPATCH_ATTN64_LAUNCHES 8         /* one-kernel attention halves of the stage-1 blocks (attn_block.hip) */
+#define PF_DISPATCH_MIT_MLP_FUSED_LAUNCHES 9  /* one-kernel Mlps of MiT stages 1 / 2 (mit_mlp.hip) */
+#define PF_DISPATCH_LN_KERNEL_LAUNCHES 10     /* stand-alone LayerNorm launches */
+#define PF_DISPATCH_CONV_LAUNCHES 11          /* launches through the engine's conv / linear dispatcher (all tile kinds, Winograd included) */
+#define PF_DISPATCH_SB_TENSORS 12             /* activations allocated as split planes (PF_SBA, PF_SBA_HEADS, the exact scheme's ParamNet) */
+#define PF_DISPATCH_FORKS 13                  /* fork windows: copies of the workspace allocator handed to a side stream */
+#define PF_DISPATCH_FORK_ALLOC_CONFLICTS 14   /* fork windows in which BOTH the copy and the parent allocated (two streams, one scratch offset): must be 0 */
+#define PF_DISPATCH_REAL_PEAK_BYTES 15        /* what the forward allocated from the workspace (main region + ParamNet region) */
+#define PF_DISPATCH_DRY_PEAK_BYTES 16         /* what pf_workspace_bytes' dry run sized for them; real > dry in either region: the call returns PF_ERR_WORKSPACE */
+#define PF_DISPATCH_COLS 17
+int pf_last_dispatch(pf_handle h, int64_t* out, int n);
+
 /* The same for a whole batch in one launch per 32 images (the reference's per-image Python loop,
  * gravity_head.py:244-260 / latitude_head.py:201-218): h_hw = HOST array [B][2] of (H, W); h_up_out / h_lat_out = HOST
  * arrays of B DEVICE pointers ([2][H][W] and [H][W] each).  Classification arch: workspace of B*3*320*320 floats. */

@@ -121,9 +121,13 @@ struct Ctx {
   float* tune_scratch = nullptr;  // [max_conv_out] floats, followed by 3 bf16 planes of max_conv_out elements
   size_t tune_scratch_elems = 0;
   size_t max_conv_out = 0;  // elements of the largest (grouped) conv output seen by the dry run = tuning scratch size
+  size_t nalloc = 0;        // alloc() calls so far: a fork window (pf_engine::fork_open) compares it at the fork and at the join
+  int64_t* rep = nullptr;   // the engine's dispatch report (PF_DISPATCH_*: host counters of the real forward; nullptr in dry runs and probes)
+  void count(int col, int64_t n = 1) { if (rep) rep[col] += n; }
   float* alloc(size_t nfloats) {
     const size_t bytes = (nfloats * 4 + 255) & ~(size_t)255;
     const size_t o = off;
+    ++nalloc;
     off += bytes;
     if (off > peak) peak = off;
     return reinterpret_cast<float*>(base + o);
@@ -132,6 +136,7 @@ struct Ctx {
   SbT alloc_sb(size_t elems) {
     SbT t;
     const size_t stride = (elems + 127) & ~(size_t)127;
+    count(PF_DISPATCH_SB_TENSORS);
     t.p = reinterpret_cast<unsigned short*>(alloc((sb_planes * stride * 2 + 3) / 4));
     t.plane = stride | (sb_planes == 2 ? SB_FMT_F16 : 0);
     return t;
@@ -310,6 +315,27 @@ struct pf_engine {
     if (side_stream_mode >= 2 && !side2 && hipStreamCreateWithFlags(&side2, hipStreamNonBlocking) != hipSuccess) { side2 = nullptr; return false; }
     return true;
   }
+  // A FORK WINDOW runs from a `Ctx c2 = c` -- a COPY of the bump allocator that issues launches on a side stream -- to the join of that stream.  Both contexts
+  // continue from ONE offset, so the window is sound only while at most one of them allocates (the normal case: the parent's split-K partial for the sr conv while q
+  // runs on the side stream).  Both allocating would hand two streams the same scratch: counted, timing-free, in PF_DISPATCH_FORK_ALLOC_CONFLICTS -- 0 after every forward.
+  struct ForkWin { bool open = false, side_alloced = false; size_t nalloc0 = 0; };
+  ForkWin fw_q, fw_ll;   // q beside kv / the stage-3 split (never nested in each other); the low-level encoder beside stages 3 / 4
+  Ctx fork_open(Ctx& c, hipStream_t s, ForkWin& w) {
+    Ctx c2 = c;
+    c2.s = s;
+    w.open = true; w.side_alloced = false; w.nalloc0 = c.nalloc;
+    c.count(PF_DISPATCH_FORKS);
+    return c2;
+  }
+  void fork_side_done(ForkWin& w, const Ctx& c2) { w.side_alloced = c2.nalloc > w.nalloc0; }  // the side stream's launches are issued
+  void fork_join(Ctx& c, ForkWin& w) {
+    if (!w.open) return;
+    if (w.side_alloced && c.nalloc > w.nalloc0) c.count(PF_DISPATCH_FORK_ALLOC_CONFLICTS);
+    w.open = false;
+  }
+  int64_t dispatch[PF_DISPATCH_COLS] = {};  // pf_last_dispatch: what the last forward launched
+  int splitk_mode = -1;      // PF_SPLITK: 0 = no split-K, N > 1 forces the factor (conv_splitk_shape); read per engine, so that a process can hold engines of both kinds
+  int wino_half = 1;         // PF_WINO_HALF=0: square Winograd patches always (ConvParams::wino_half)
   bool can_fork(const Ctx& c) { return side_stream_mode && !c.dry && !c.tuning && (!c.prof || c.prof->min_work > 0.0) && side_ready(); }  // (a full per-launch profile keeps one stream: its event pairs must bracket what they name)
   bool sba_heads = false;    // PF_SBA_HEADS=1: the tensors between the 3x3 convs of the decoders' ResidualConvUnits are written as split-f16 planes by the producing
                              // conv's epilogue (plus fp32 where a residual add reads them) and the halo kernel copies them (igemm_sbh ASB) instead of splitting
@@ -833,7 +859,7 @@ struct pf_engine {
       bool plain = !nchw && !ups && !w.ln_s && w.Cin % 32 == 0 && w.KWCp > 0;
       for (int g = 0; g < ngroups; ++g)
         if (calls[g].head_kind || calls[g].w->btab || calls[g].res2 || calls[g].y.s.p || !calls[g].y.f || calls[g].x.s.p) plain = false;
-      if (plain && split_bf16) splitk = conv_splitk_shape((long)B * Ho_ * Wo_, w.Cout, w.KH, w.KWCp, ngroups);
+      if (plain && split_bf16) splitk = conv_splitk_shape((long)B * Ho_ * Wo_, w.Cout, w.KH, w.KWCp, ngroups, splitk_mode);
     }
     const size_t mk_part = c.mark();
     float* part = splitk > 1 ? c.alloc((size_t)splitk * ngroups * B * Ho_ * Wo_ * w.Cout) : nullptr;
@@ -862,6 +888,7 @@ struct pf_engine {
     p.act = act; p.post_relu = post_relu; p.nchw_out = nchw;
     p.nterms = nterms;
     p.ups = ups;
+    p.wino_half = wino_half;
     p.ln = w.ln_s ? 1 : 0; p.ln_eps = w.ln_eps;
     p.sat = (c.tuning || c.dry) ? nullptr : d_sat; p.sat_limit = w.sat_limit;
     for (int g = 1; g < ngroups; ++g) p.sat_limit = std::min(p.sat_limit, calls[g].w->sat_limit);
@@ -895,6 +922,7 @@ struct pf_engine {
       }
     }
     ProfScope ps(c.prof, c.s, conv_tile_is_sb(tile) ? PC_IGEMM_SB : PC_IGEMM, 2.0 * ngroups * p.M * (double)w.Cout * w.KH * w.KW * w.CinReal, p.M * ngroups, w.Cout, w.KH * w.KW * w.CinReal, w.KH);
+    c.count(PF_DISPATCH_CONV_LAUNCHES);
     launch_conv_tile(p, tile, c.s);
   }
   // Measure, don't guess: run the launch with every tile configuration (outputs redirected to scratch so in-place
@@ -948,6 +976,7 @@ struct pf_engine {
   // y.f may alias x; y may carry fp32, split planes, or both
   void ln(Ctx& c, const LNW& l, const float* x, Ten y, long rows) {
     if (c.dry) return;
+    c.count(PF_DISPATCH_LN_KERNEL_LAUNCHES);
     ProfScope ps(c.prof, c.s, PC_LAYERNORM, (4.0 + (y.f ? 4.0 : 0.0) + (y.s.p ? 6.0 : 0.0)) * rows * l.C);
     launch_layernorm(x, l.g, l.b, y.f, rows, l.C, l.eps, c.s, y.s.p, y.s.plane);
   }
@@ -962,6 +991,7 @@ struct pf_engine {
     a.M = (int)M; a.tokens = tokens; a.bpi = (tokens + 63) / 64; a.N = r.N; a.act = act;
     a.sat = d_sat; a.sat_limit = r.sat_limit;
     ProfScope ps(c.prof, c.s, PC_IGEMM_SB, 2.0 * M * (double)r.N * r.K, (int)M, r.N, r.K, 1);
+    c.count(PF_DISPATCH_RB_LAUNCHES);
     launch_rb_linear(a, r.K, c.s);
   }
 
@@ -972,6 +1002,7 @@ struct pf_engine {
     ThinLinArgs a;
     a.x = x; a.res = res; a.y = y; a.wfr = wfr; a.tab = tab; a.M = M; a.sat = d_sat; a.sat_limit = sat_limit;
     ProfScope ps(c.prof, c.s, PC_IGEMM_SB, 2.0 * M * 128.0 * 128.0, (int)M, 128, 128, 1);
+    c.count(PF_DISPATCH_THIN128_LAUNCHES);
     launch_thin128(a, num_cus, c.s);
   }
 
@@ -1008,10 +1039,10 @@ struct pf_engine {
       if (s == 2 && llf && B >= 4 && side_stream_mode >= 2 && can_fork(c)) {  // PF_SIDE_STREAM=2 (measured: no gain)  // the low-level encoder conv (a full-chip launch of its own) next to the small launches of stages 3 / 4
         (void)hipEventRecord(ev_ll, c.s);  // x0 is long since ready; the event only orders the side stream behind this forward's beginning
         (void)hipStreamWaitEvent(side2, ev_ll, 0);
-        Ctx c2 = c;
-        c2.s = side2;
+        Ctx c2 = fork_open(c, side2, fw_ll);
         conv(c2, ll, Ten(const_cast<float*>(x0)), B, NET, NET, *llf, ACT_RELU);
         (void)hipEventRecord(ev_ll, side2);
+        fork_side_done(fw_ll, c2);
         ll_forked = true;
       }
       if (s == 0 && pe_s7_w && nterms == NT_F16X3 && !c.tuning && cur.f) {
@@ -1050,10 +1081,10 @@ struct pf_engine {
           if (fork) {
             (void)hipEventRecord(ev_fork, c.s);
             (void)hipStreamWaitEvent(side, ev_fork, 0);
-            Ctx c2 = c;
-            c2.s = side;
+            Ctx c2 = fork_open(c, side, fw_q);
             gemm(c2, mb.qln, Ten(x), M, Ten(qb));
             (void)hipEventRecord(ev_join, side);
+            fork_side_done(fw_q, c2);
           } else {
             gemm(c, mb.qln, Ten(x), M, Ten(qb));
           }
@@ -1065,6 +1096,7 @@ struct pf_engine {
             a.srn_g = mb.srn.g; a.srn_b = mb.srn.b; a.srn_eps = mb.srn.eps; a.kv_inv = mb.rsrkv.kv_inv; a.kv_bias = mb.rsrkv.kv_b;
             a.kv = kvb; a.B = B; a.Hr = kvh; a.Wr = kvw; a.bpi = (kvh * kvw + 31) / 32; a.sat = d_sat;
             ProfScope ps(c.prof, c.s, PC_IGEMM_SB, 2.0 * Mkv * (double)C * (sr * sr * C + 2 * C), (int)Mkv, 3 * C, sr * sr * C + 2 * C, sr);
+            c.count(PF_DISPATCH_RB_LAUNCHES);
             launch_rb_srkv(a, C, c.s);
           }
         } else if (sr > 1 && fuse64) {
@@ -1083,10 +1115,10 @@ struct pf_engine {
           if (use_rb && (rb_chain & 1) && fork) {  // q = LN1(x) Wq with the LayerNorm inside the kernel: independent of the LayerNorm launch below
             (void)hipEventRecord(ev_fork, c.s);
             (void)hipStreamWaitEvent(side, ev_fork, 0);
-            Ctx c2 = c;
-            c2.s = side;
+            Ctx c2 = fork_open(c, side, fw_q);
             rb_linear(c2, mb.rq, x, M, (int)N, qb, &mb.n1);
             (void)hipEventRecord(ev_join, side);
+            fork_side_done(fw_q, c2);
           }
           ln(c, mb.n1, x, xn, M);
           if (use_rb && (rb_chain & 1)) {
@@ -1094,10 +1126,10 @@ struct pf_engine {
           } else if (fork) {  // q projection next to sr conv + kv GEMM: both read xn, attention needs both
             (void)hipEventRecord(ev_fork, c.s);
             (void)hipStreamWaitEvent(side, ev_fork, 0);
-            Ctx c2 = c;
-            c2.s = side;
+            Ctx c2 = fork_open(c, side, fw_q);
             if (thin_q) thin(c2, mb.tq_w, mb.tq_tab, xn.f, nullptr, qb, M, mb.q.sat_limit, "q"); else gemm(c2, mb.q, xn, M, Ten(qb));
             (void)hipEventRecord(ev_join, side);
+            fork_side_done(fw_q, c2);
           } else {
             if (thin_q) thin(c, mb.tq_w, mb.tq_tab, xn.f, nullptr, qb, M, mb.q.sat_limit, "q"); else gemm(c, mb.q, xn, M, Ten(qb));
           }
@@ -1114,10 +1146,10 @@ struct pf_engine {
           if (B >= 4 && (may_fork && can_fork(c))) {                // norm1 inside both of its consumers; q next to kv
             (void)hipEventRecord(ev_fork, c.s);
             (void)hipStreamWaitEvent(side, ev_fork, 0);
-            Ctx c2 = c;
-            c2.s = side;
+            Ctx c2 = fork_open(c, side, fw_q);
             gemm(c2, mb.q, Ten(x), M, Ten(qb));
             (void)hipEventRecord(ev_join, side);
+            fork_side_done(fw_q, c2);
           } else {
             gemm(c, mb.q, Ten(x), M, Ten(qb));
           }
@@ -1128,6 +1160,7 @@ struct pf_engine {
           gemm(c, mb.kv, xn, M, Ten(kvb));
         }
         if (!fuse64 && B >= 4 && (sr > 1 || (mb.q.ln_s && mb.kv.ln_s)) && (may_fork && can_fork(c))) (void)hipStreamWaitEvent(c.s, ev_join, 0);
+        if (may_fork) fork_join(c, fw_q);  // (the stage-3 split keeps ITS window open over all blocks)
         if (c.dbg && c.dbg->range) {
           if (!fuse64) range_in(c, fmt("attention s%d.b%d q", s + 1, blk), qb, (size_t)M * C);   // (fused: q never leaves the registers; the kernel watches it against the same window)
           range_in(c, fmt("attention s%d.b%d kv", s + 1, blk), kvb, (size_t)Mkv * 2 * C);
@@ -1139,6 +1172,7 @@ struct pf_engine {
             a.x = x; a.kv = kvb; a.y = x; a.wfr = mb.a64_w; a.tab = mb.a64_tab; a.B = B; a.N = (int)N; a.M = kvh * kvw; a.ln_eps = mb.n1.eps; a.sat = d_sat; a.sat_limit = mb.proj.sat_limit;
             // work = q + proj (2 x 2 M C C) + QK^T + PV (4 M C kv)
             ProfScope ps(c.prof, c.s, PC_ATTN, 4.0 * M * C * (double)C + 4.0 * M * C * (kvh * kvw));
+            c.count(PF_DISPATCH_ATTN64_LAUNCHES);
             launch_mit_attn64(a, num_cus, c.s);
           }
         }
@@ -1156,6 +1190,7 @@ struct pf_engine {
             a.ln2_g = mb.n2.g; a.ln2_b = mb.n2.b; a.ln2_eps = mb.n2.eps; a.fc1_inv = mb.rfc1.inv; a.fc1_bias = mb.rfc1.b; a.hidden = hb;
             a.B = B; a.tokens = (int)N; a.bpi = ((int)N + 63) / 64; a.sat = d_sat;
             ProfScope ps(c.prof, c.s, PC_IGEMM_SB, 2.0 * M * (double)C * 5 * C, (int)M, 5 * C, C, 1);
+            c.count(PF_DISPATCH_RB_LAUNCHES);
             launch_rb_proj_fc1(a, C, c.s);
           }
         } else if (use_rb && (rb_chain & 4)) rb_linear(c, mb.rproj, ab.f, M, (int)N, x, nullptr, ACT_NONE, x);
@@ -1167,6 +1202,7 @@ struct pf_engine {
           range_in(c, fmt("mit_mlp s%d.b%d x (LN-fused)", s + 1, blk), x, (size_t)M * C);
           if (!c.dry) {
             ProfScope ps(c.prof, c.s, PC_IGEMM_SB, 2.0 * 2.0 * M * (double)C * 4 * C, (int)M, C, 8 * C, 9);
+            c.count(PF_DISPATCH_MIT_MLP_FUSED_LAUNCHES);
             launch_mit_mlp(x, xalt, mb.mlp_w, mb.mlp_tab, B, Ho, Wo, C, mb.n2.eps, c.s, d_sat, 65504.f);
           }
           std::swap(x, xalt);
@@ -1192,22 +1228,37 @@ struct pf_engine {
       // a single round whose time is a block's latency (prologue, K loop at one wave per SIMD, epilogue) -- the chip idles in every prologue, epilogue and launch gap.
       // Images are independent, so the batch is cut in two halves that walk the stage on TWO streams (the caller's and `side`, which gives up the q-beside-kv fork
       // for it: no additional hardware queue): two desynchronised chains of half-size launches fill each other's gaps.  Same kernels, same per-image arithmetic:
-      // bit-identical results (tests/test_gpu_e2e.py::test_stage3_batch_split_is_bit_identical).
+      // bit-identical to the one-stream walk (tests/test_gpu_r06.py::test_stage3_batch_split_is_bit_identical) wherever the LayerNorm-fused q GEMM, the one launch of
+      // a block that goes through the row-count-keyed tile table, gets the same tile for M / 2 rows as for M (B = 32); at B = 64 the table has sb128x64 for 25 600
+      // rows and sb64x64f2 for 12 800 (other roundings; with ONE tile forced for both, PF_CONV_TILE without a table, the walks are bit-identical): 1-cos 6e-8 between the
+      // two walks (tests/test_gpu_batch_dispatch.py).
       // Measured (same box, profiles/r06_s3_split.md): batch 64 (two halves of 224 blocks, each a full round of its own) +2.2 %; batch 32 (halves of 112 blocks) -0.3 ... -1.8 %:
       // a half-size launch takes as long as the full one (a launch IS a block's latency), so the split pays only when EACH half still fills the chip -- the gate below
       // is the row-block form's gate taken for the half batch (PF_S3_SPLIT=2 forces the split whenever the whole batch passes it: the batch-32 A/B).
       const long rb_all = (long)B * ((N + 63) / 64), rb_half = rb_all / 2;
       auto rb_gate = [&](long nb) { return nb >= rb_min_blocks && (nb % num_cus == 0 || nb % num_cus >= num_cus * 3 / 4); };
-      const bool split = s3_split && s == 2 && sr > 1 && !S && !fused_mlp && B >= 16 && B % 2 == 0 && !c.dry && !c.dbg && !c.tuning && !st.blocks.empty() && rb_chain && nterms == NT_F16X3 &&
+      bool split = s3_split && s == 2 && sr > 1 && !S && !fused_mlp && B >= 16 && B % 2 == 0 && !c.dry && !c.dbg && !c.tuning && !st.blocks.empty() && rb_chain && nterms == NT_F16X3 &&
                          st.blocks[0].rq.w && rb_gate(rb_all) && (s3_split >= 2 || rb_gate(rb_half)) && can_fork(c);
+      // The second half walks the stage on a COPY of the bump allocator (a fork window, see fork_open): the split is sound only if a half-batch block allocates
+      // NOTHING.  That holds for the default forms (key / value branch as one launch, LayerNorm-fused or row-block linears), but not for every PF_* combination: with
+      // PF_FUSE_LN=0, or PF_RB_CHAIN without bit 32, each half runs the sr conv through conv_g, whose split-K partial (M = 3 200 rows at B = 64) both streams would
+      // take from the same offset -- and which the unsplit dry run never sized.  So the gate ASKS: a dry walk of one block at the half batch (all blocks of the stage
+      // have one shape; host arithmetic only, no launch) must leave the allocator untouched, whatever the switches are; otherwise the stage runs unsplit.
+      if (split) {
+        Ctx probe = c;
+        probe.dry = true; probe.rep = nullptr;
+        float *px = x, *none = nullptr;
+        one_block(probe, st.blocks[0], 0, B / 2, M / 2, Mkv / 2, px, none, xn, qb, ab, srb, srn, kvb, hb, h2, B, false);
+        if (probe.nalloc != c.nalloc) split = false;
+      }
       int blk = -1;
       if (split) {
         const int Bh = B / 2;
         const long Mh = M / 2, Mkvh = Mkv / 2;
+        c.count(PF_DISPATCH_S3_SPLIT_TAKEN);
         (void)hipEventRecord(ev_fork, c.s);
         (void)hipStreamWaitEvent(side, ev_fork, 0);
-        Ctx c2 = c;
-        c2.s = side;
+        Ctx c2 = fork_open(c, side, fw_q);
         float* x2 = x + Mh * C;
         float* none = nullptr;
         for (MitBlock& mb : st.blocks) {
@@ -1218,6 +1269,8 @@ struct pf_engine {
         }
         (void)hipEventRecord(ev_join, side);
         (void)hipStreamWaitEvent(c.s, ev_join, 0);
+        fork_side_done(fw_q, c2);
+        fork_join(c, fw_q);
       } else {
         for (MitBlock& mb : st.blocks) {
           if (blk >= 0) tap(c, fmt("mit.s%d.b%d", s + 1, blk), x, B, Ho, Wo, C);  // the previous block's output (token stream, pre stage norm)
@@ -1418,7 +1471,7 @@ struct pf_engine {
     ll_forked = false;
     mit(c, B, x0, feats, &llf);
     if (!c.dry && c.prof) c.prof->mark(PH_LL, c.s);
-    if (ll_forked) (void)hipStreamWaitEvent(c.s, ev_ll, 0);
+    if (ll_forked) { (void)hipStreamWaitEvent(c.s, ev_ll, 0); fork_join(c, fw_ll); }
     else if (ll_s7_w && nterms == NT_F16X3 && !c.tuning && llf.f && !llf.s.p) stem(c, ll_s7_w, ll_s7_tab, x0, llf.f, B, NET, NET, 2, true, false, 0.f, ll.sat_limit, "low-level encoder");
     else conv(c, ll, Ten(x0), B, NET, NET, llf, ACT_RELU);  // BN folded (perspectivefields.py:79-83)
     tap(c, "ll", llf.f, B, NET / 2, NET / 2, LL_CH);
@@ -1473,6 +1526,7 @@ struct pf_engine {
     if (cp.max_conv_out > c.max_conv_out) c.max_conv_out = cp.max_conv_out;
   }
   size_t run_pn_peak = 0;
+  std::map<int, size_t> pn_peak;  // batch -> bytes of the ParamNet region as the dry run sized it
 
   // with_scratch: plus the target of the tuning launches (largest conv output as fp32 + 3 bf16 planes) -- pf_autotune only
   size_t workspace_bytes(int B, bool with_scratch = false) {
@@ -1483,6 +1537,7 @@ struct pf_engine {
       run(c, B, nullptr, true, nullptr, nullptr, nullptr);
       const size_t main_peak = (c.peak + 255) & ~(size_t)255, total = main_peak + ((run_pn_peak + 255) & ~(size_t)255);
       pn_off[B] = main_peak;
+      pn_peak[B] = (run_pn_peak + 255) & ~(size_t)255;
       ws_cache[B] = total + 4096;
       scratch_off[B] = total;
       scratch_elems[B] = c.max_conv_out;
@@ -1512,9 +1567,27 @@ struct pf_engine {
       c.tune_scratch = reinterpret_cast<float*>(base + scratch_off[B]);
       c.tune_scratch_elems = scratch_elems[B];
     }
+    std::fill(dispatch, dispatch + PF_DISPATCH_COLS, (int64_t)0);
+    if (!tune) c.rep = dispatch;
+    const LaunchCounts lc0 = g_launch_counts;
+    g_launch_counts.splitk_max = 0;
+    fw_q.open = fw_ll.open = false;
     run(c, B, in, is_u8, pg, pl, params);
+    const LaunchCounts lc1 = g_launch_counts;
+    g_launch_counts.splitk_max = std::max(lc0.splitk_max, lc1.splitk_max);
+    dispatch[PF_DISPATCH_BATCH] = B;
+    dispatch[PF_DISPATCH_SPLITK_LAUNCHES] = lc1.splitk - lc0.splitk;
+    dispatch[PF_DISPATCH_SPLITK_MAX_FACTOR] = lc1.splitk_max;
+    dispatch[PF_DISPATCH_WINO_LAUNCHES] = lc1.wino - lc0.wino;
+    dispatch[PF_DISPATCH_WINO_HALF_LAUNCHES] = lc1.wino_half - lc0.wino_half;
+    // the dry run promised the caller's buffer two regions (main, ParamNet behind it at pn_off): the real run must have stayed inside both
+    const size_t real_main = (c.peak + 255) & ~(size_t)255, real_pn = (run_pn_peak + 255) & ~(size_t)255;
+    dispatch[PF_DISPATCH_REAL_PEAK_BYTES] = (int64_t)(real_main + real_pn);
+    dispatch[PF_DISPATCH_DRY_PEAK_BYTES] = (int64_t)(pn_off[B] + pn_peak[B]);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(PF_ERR_DEVICE, fmt("kernel launch failed: %s", hipGetErrorString(e)));
+    if (real_main > pn_off[B] || real_pn > pn_peak[B])
+      return fail(PF_ERR_WORKSPACE, fmt("the forward allocated past what pf_workspace_bytes(%d) sized: main region %zu > %zu or ParamNet region %zu > %zu bytes (the launches were issued: the workspace and outputs of this call are not to be trusted)", B, real_main, pn_off[B], real_pn, pn_peak[B]));
     return PF_OK;
   }
 };
@@ -1582,6 +1655,8 @@ int pf_create(pf_handle* out, int device, int arch) {
   if (const char* v = getenv("PF_AUTOTUNE")) e->autotune = atoi(v) != 0;
   if (const char* v = getenv("PF_SPLIT_BF16")) e->split_bf16 = atoi(v) != 0;
   if (const char* v = getenv("PF_SBA")) e->sba = atoi(v) != 0;
+  e->splitk_mode = conv_splitk_env();
+  e->wino_half = conv_wino_half_env();
   if (!e->split_bf16) e->sba = false;  // split planes are only read by the split-bf16 kernels
   if (!e->split_bf16 || e->sba) e->fuse_ln = false;  // the fused form lives in the split GEMM kernels and reads fp32 rows
   if (!e->split_bf16 || e->sba) e->fuse_cnx_mlp = false;
@@ -1681,6 +1756,12 @@ int pf_output_info(pf_handle h, int* g, int* l, int* p) {
 }
 
 int pf_max_batch(void) { return PF_MAX_BATCH; }
+
+int pf_last_dispatch(pf_handle h, int64_t* out, int n) {
+  if (!h || !out || n < PF_DISPATCH_COLS) return h ? h->fail(PF_ERR_ARG, "pf_last_dispatch: the array must hold PF_DISPATCH_COLS entries") : PF_ERR_ARG;
+  std::copy(h->dispatch, h->dispatch + PF_DISPATCH_COLS, out);
+  return PF_OK;
+}
 
 size_t pf_workspace_bytes(pf_handle h, int batch) {
   if (!h || batch <= 0 || batch > PF_MAX_BATCH) return 0;

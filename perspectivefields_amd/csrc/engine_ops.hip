@@ -49,6 +49,7 @@ int pf_op_conv2d(int device, const float* x, const float* x2, int B, int H, int 
   p.nterms = precision == PF_PRECISION_FP32_BF16X6 ? 6 : NT_F16X3;
   // split-plane INPUT: the plane format (bit 0 of x_plane_elems, sb_split.h) fixes the scheme: fp16 planes <-> split-f16, bf16 planes <-> bf16 schemes
   if (x_planes) p.nterms = (x_plane_elems & 1) ? NT_F16X3 : (p.nterms == NT_F16X3 ? 6 : p.nterms);
+  p.wino_half = conv_wino_half_env();
   p.finish();
   if ((!x && !x_planes) || (!y && !y_planes) || (C2 > 0 && !x2 && !x2_planes)) { g_create_error = "pf_op_conv2d: missing input or output"; return PF_ERR_ARG; }
   // an explicit tile that cannot read / write split planes is an error; with fp32 operands an unusable tile id falls back to the cost model
@@ -409,6 +410,7 @@ int pf_op_conv2d_bench(int device, int B, int H, int W, int Cin, int Cout, int K
   p.B = B; p.H = H; p.W = W; p.C1 = Cin; p.C2 = 0; p.KH = K; p.KW = K; p.stride = stride; p.pad = pad;
   p.Cout = Cout; p.act = ACT_RELU; p.post_relu = 0; p.nchw_out = 0;
   p.nterms = precision == PF_PRECISION_FP32_BF16X6 ? 6 : NT_F16X3;
+  p.wino_half = conv_wino_half_env();
   p.finish();
   const size_t nx = (size_t)B * H * W * Cin, nw = (size_t)Cout * K * p.KWCp, ny = (size_t)p.M * Cout;
   float *dx = nullptr, *dw = nullptr, *dy = nullptr, *db = nullptr;

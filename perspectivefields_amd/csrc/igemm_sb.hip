@@ -119,16 +119,16 @@ bool conv_sb_tile_ok(const ConvParams& p, int sb_tile) {
   return !p.ups;
 }
 
-static int g_splitk_env = -2;  // PF_SPLITK=0 disables split-K, N > 1 forces the factor (tuning aid)
+thread_local LaunchCounts g_launch_counts;
+int conv_splitk_env() { const char* e = getenv("PF_SPLITK"); return e ? atoi(e) : -1; }  // PF_SPLITK=0 disables split-K, N > 1 forces the factor (tuning aid)
 // shape-only part (the engine's workspace dry run uses it before any pointer exists): deep K (>= 32 steps of 32) and at most 300
 // tiles of 64x64, i.e. barely one block per CU -- enough slices for ~1024 blocks, each keeping >= 8 K steps
-int conv_splitk_shape(long M, int Cout, int KH, int KWCp, int groups) {
-  if (g_splitk_env == -2) { const char* e = getenv("PF_SPLITK"); g_splitk_env = e ? atoi(e) : -1; }
-  if (g_splitk_env == 0 || (Cout & 3)) return 1;
+int conv_splitk_shape(long M, int Cout, int KH, int KWCp, int groups, int mode) {
+  if (mode == 0 || (Cout & 3)) return 1;
   const int nK = KH * (KWCp / BK);
   const long blocks64 = ((M + 63) / 64) * ((Cout + 63) / 64) * groups;
   if (nK < 32 || blocks64 > 300) return 1;
-  int S = g_splitk_env > 1 ? g_splitk_env : (int)std::min<long>(8, 1024 / blocks64);
+  int S = mode > 1 ? mode : (int)std::min<long>(8, 1024 / blocks64);
   while (S > 1 && nK / S < 8) --S;
   return S;
 }
@@ -136,7 +136,7 @@ int conv_splitk_factor(const ConvParams& p) {
   if (p.nchw_out || p.ups || p.ln || (p.Cin % BK) != 0 || !conv_sb_eligible(p)) return 1;
   for (int g = 0; g < p.groups; ++g)
     if (p.g[g].head_kind || p.g[g].bias_tab || p.g[g].res2 || p.g[g].y_sb || !p.g[g].y) return 1;
-  return conv_splitk_shape(p.M, p.Cout, p.KH, p.KWCp, p.groups);
+  return conv_splitk_shape(p.M, p.Cout, p.KH, p.KWCp, p.groups, conv_splitk_env());
 }
 
 // y = post(act(oscale * sum_s partial[s] + bias) + res1), 4 outputs per thread
@@ -160,6 +160,7 @@ void launch_conv_sb(const ConvParams& p0, int sb_tile, hipStream_t s) {
   ConvParams p = p0;
   // split-K only on the linear tiles, with scratch from the caller and 16-byte rows
   if (p.splitk > 1 && (sb_tile >= 12 /* halo tiles and, in tuning builds, the linear tiles' tuning forms */ || p.ln || !p.g[0].partial || (p.groups > 1 && !p.g[1].partial) || (p.Cout & 3) || p.ldy != p.Cout)) p.splitk = 1;
+  if (p.splitk > 1) { ++g_launch_counts.splitk; g_launch_counts.splitk_max = std::max<long>(g_launch_counts.splitk_max, p.splitk); }
   struct Reduce { const ConvParams& p; hipStream_t s; ~Reduce() {
     if (p.splitk <= 1) return;
     const long mn4 = (long)p.M * p.Cout / 4;

@@ -118,6 +118,8 @@ struct ConvParams {
   // CONSUMER's window: 65504, 65504 / 4 in front of a Winograd conv (wino.hip), 8188 / 4094 for the attention operands q / kv (attn.hip).
   unsigned* sat = nullptr;
   float sat_limit = 65504.f;
+  int wino_half = 1;  // Winograd launches: non-zero = the half-patch geometry where it applies (wino.hip), 0 = square patches always (PF_WINO_HALF: the engine sets what its
+                      // pf_create read, the conv op entry points what conv_wino_half_env() says at the call)
   unsigned long long* stamps = nullptr;  // timing aid (wino.hip, PF_WINO_STAMPS=1 in pf_op_conv2d_bench): s_memtime stamps of block 17, [wave][128]
   // fills the derived fields (Ho, Wo, M, Cin, *_bytes) from the primary ones
   void finish() {
@@ -154,7 +156,13 @@ void launch_conv_sb(const ConvParams& p, int sb_tile, hipStream_t s);
 // split-K factor for a launch (1 = none): deep-K shapes whose 64x64 tiling gives too few blocks for 256 CUs (the MiT spatial-
 // reduction convs: 3 200 rows, K up to 4 096); the caller allocates g[].partial = splitk * M * ldy floats and sets ConvParams::splitk
 int conv_splitk_factor(const ConvParams& p);
-int conv_splitk_shape(long M, int Cout, int KH, int KWCp, int groups);  // its shape-only part
+int conv_splitk_shape(long M, int Cout, int KH, int KWCp, int groups, int mode);  // its shape-only part; mode = PF_SPLITK (conv_splitk_env): -1 default, 0 never, N > 1 forces the factor
+int conv_wino_half_env();  // PF_WINO_HALF (default 1) as the environment has it NOW
+int conv_splitk_env();  // PF_SPLITK as the environment has it NOW (pf_create reads it per engine, the op entry points per call: tests switch it inside one process)
+// What the launchers of this thread really did (plain host increments, no device work): the decisions taken below the engine -- split-K after launch_conv_sb's
+// own checks, the Winograd geometry -- for the engine's dispatch report (pf_last_dispatch), which takes the difference over one forward
+struct LaunchCounts { long splitk = 0, splitk_max = 0, wino = 0, wino_half = 0; };
+extern thread_local LaunchCounts g_launch_counts;
 const char* conv_tile_name(int tile_id);
 // Winograd F(2x2, 3x3) kernel (wino.hip; tiles "wino256x64d" / "wino256x64c" of the split family)
 bool conv_wino_ok(const ConvParams& p);

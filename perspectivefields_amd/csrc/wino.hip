@@ -629,10 +629,10 @@ bool conv_wino_ok(const ConvParams& p) {
   return true;
 }
 
+int conv_wino_half_env() { const char* e = getenv("PF_WINO_HALF"); return e ? atoi(e) : 1; }
 static bool wino_half_geometry(const ConvParams& p) {
-  static const int half_env = [] { const char* e = getenv("PF_WINO_HALF"); return e ? atoi(e) : 1; }();
   const int rem = p.Ho % W_PY;
-  return half_env && rem >= 1 && rem <= 8;
+  return p.wino_half && rem >= 1 && rem <= 8;
 }
 int conv_wino_blocks(const ConvParams& p) {
   const int tilesN = p.Cout / W_BN, tilesX = (p.Wo + W_PX - 1) / W_PX;
@@ -643,6 +643,7 @@ int conv_wino_blocks(const ConvParams& p) {
 void launch_conv_wino(const ConvParams& p, hipStream_t s, int variant) {
   const int tilesN = p.Cout / W_BN, tilesX = (p.Wo + W_PX - 1) / W_PX, tilesY = (p.Ho + W_PY - 1) / W_PY;
   const dim3 grid(p.B * tilesY * tilesX * tilesN * p.groups);
+  ++g_launch_counts.wino;
   if (variant == 1) {  // "wino256x64d"
 #ifdef PF_TUNING_BUILD
     static int dabl = -1;
@@ -664,6 +665,7 @@ void launch_conv_wino(const ConvParams& p, hipStream_t s, int variant) {
 #endif
     // Half-patch geometry where the square patches would waste half a patch row: 1 <= Ho mod 16 <= 8 (the decoders' 40 x 40 maps; PF_WINO_HALF=0: square patches always)
     if (wino_half_geometry(p) && !p.stamps) {
+      ++g_launch_counts.wino_half;
       const int nhalf = p.B * ((p.Ho + 7) / 8) * tilesX;
       hipLaunchKernelGGL((wino4d_f2x2_kernel<false, 0, true>), dim3(((nhalf + 1) / 2) * tilesN * p.groups), dim3(W4_NT), 0, s, p);
       return;

@@ -20,6 +20,10 @@ NET = 320
 PARAMS_STRIDE = 8
 
 PF_OK = 0
+# columns of pf_last_dispatch (include/pf_hip.h PF_DISPATCH_*), in order
+DISPATCH_COLUMNS = ("batch", "s3_split_taken", "rb_launches", "splitk_launches", "splitk_max_factor", "wino_launches", "wino_half_launches", "thin128_launches",
+                    "attn64_launches", "mit_mlp_fused_launches", "ln_kernel_launches", "conv_launches", "sb_tensors", "forks", "fork_alloc_conflicts",
+                    "real_peak_bytes", "dry_peak_bytes")
 _STATUS = {0: "PF_OK", -1: "PF_ERR_ARG", -2: "PF_ERR_DEVICE", -3: "PF_ERR_WEIGHTS", -4: "PF_ERR_WORKSPACE"}
 
 # every symbol include/pf_hip.h declares: name -> (restype, argtypes)
@@ -35,6 +39,7 @@ _SIGNATURES = {
     "pf_output_info": (_c.c_int, [_P, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "pf_max_batch": (_c.c_int, []),
     "pf_workspace_bytes": (_c.c_size_t, [_P, _c.c_int]),
+    "pf_last_dispatch": (_c.c_int, [_P, _c.POINTER(_c.c_int64), _c.c_int]),
     "pf_forward_u8": (_c.c_int, [_P, _c.c_int, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
     "pf_forward_f32": (_c.c_int, [_P, _c.c_int, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
     "pf_set_saturation_counter": (_c.c_int, [_P, _P]),
@@ -283,6 +288,14 @@ class Engine:
     # ---------------------------------------------------------------- forward
     def workspace_bytes(self, batch: int) -> int:
         return int(self.lib.pf_workspace_bytes(self._h, batch))
+
+    def last_dispatch(self) -> Dict[str, int]:
+        """What the last eager forward of this engine launched (pf_last_dispatch): host-side counters of the batch- and switch-dependent decisions -- the stage-3 split,
+        row-block / split-K / Winograd / fused-block launches, fork windows to the side stream and whether two streams allocated from one offset
+        (`fork_alloc_conflicts`, must be 0), and the workspace the forward really took against what the dry run sized.  No device work, no synchronisation."""
+        out = (ctypes.c_int64 * len(DISPATCH_COLUMNS))()
+        _check(self.lib.pf_last_dispatch(self._h, out, len(DISPATCH_COLUMNS)), self._h, "pf_last_dispatch")
+        return dict(zip(DISPATCH_COLUMNS, (int(v) for v in out)))
 
     def set_defer_params(self, on: bool):
         """Deferred ParamNet branch (pf_set_defer_params): the camera-parameter tensor of a forward is complete in stream order once the NEXT forward has been issued

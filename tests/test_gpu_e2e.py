@@ -201,6 +201,11 @@ def test_fused_layernorm_agrees_with_layernorm_kernels(monkeypatch, case):
         assert c <= 1e-6 and e <= 1e-5 and d <= 5e-5
 
 
+SWITCH_WITNESS = {"PF_WINO_HALF=0": ("wino_half_launches", "zero"), "PF_WINO=0": ("wino_launches", "zero"), "PF_FUSE_MIT_MLP=0": ("mit_mlp_fused_launches", "zero"),
+                  "PF_SIDE_STREAM=0": ("forks", "zero"), "PF_SIDE_STREAM=2": ("forks", "plus1"), "PF_ATTN64=0": ("attn64_launches", "zero"),
+                  "PF_THIN128=1": ("thin128_launches", "more"), "PF_SBA_HEADS=1": ("sb_tensors", "more")}
+
+
 @pytest.mark.parametrize("env", ["PF_FUSE_CNX_MLP=0", "PF_FUSE_MIT_MLP=0", "PF_SIDE_STREAM=0", "PF_SIDE_STREAM=2", "PF_CNX_MLP_192=0", "PF_MIT_MLP_128=0", "PF_MIT_MLP_128=1", "PF_MIT_MLP_SB=0", "PF_SBA_HEADS=1",
                                  "PF_WINO=0", "PF_WINO_TILE=wino256x64c", "PF_WINO_HALF=0", "PF_ATTN64=0", "PF_STEM7=0", "PF_THIN128=1"])   # (PF_THIN128=1: the thin 128 -> 128 projections of stage 2 from one row up -- the default takes them from 25 600 rows, i.e. batch 16)   the direct halo tile on the 80^2 / 40^2 256 -> 256 shapes (split-f16 mode), the compiler-scheduled Winograd form, square Winograd patches on the 40^2 / 20^2 maps, stage 1 with separate q / attention / proj launches, the 7 x 7 image convs on the implicit-GEMM tiles
 def test_fused_block_mlps_and_stream_modes_agree(monkeypatch, env):
@@ -210,10 +215,18 @@ def test_fused_block_mlps_and_stream_modes_agree(monkeypatch, env):
 
     imgs = [synthetic_image(72, 96, seed=120 + i) for i in range(6)]
     base = model("centered").inference_batch(imgs)
+    base_rep = model("centered")._get_engine().last_dispatch()
     k, v = env.split("=")
     monkeypatch.setenv(k, v)
     alt_model = PerspectiveFields(CASES["centered"], weights="synthetic:0").eval().cuda()
     alt = alt_model.inference_batch(imgs)
+    alt_rep = alt_model._get_engine().last_dispatch()
+    # the switch acted (Engine.last_dispatch), for the switches whose decision the report counts: a switch cached at its first use in the process would leave the
+    # report equal to the default's and this test comparing the default engine with itself
+    col, rel = SWITCH_WITNESS.get(env, (None, None))
+    if col:
+        a, b = alt_rep[col], base_rep[col]
+        assert {"zero": a == 0 and b > 0, "more": a > b, "plus1": a == b + 1}[rel], f"{env} did not act: {col} = {a}, default {b}"
     for i, (a, b) in enumerate(zip(base, alt)):
         c = one_minus_cos(a["pred_gravity"].cpu().numpy(), b["pred_gravity"].cpu().numpy()).max()
         e = l1(a["pred_latitude"].cpu().numpy(), b["pred_latitude"].cpu().numpy())
@@ -413,14 +426,21 @@ def test_fused_prediction_heads_equal_standalone_kernel(monkeypatch):
 def test_split_k_agrees_with_single_pass(monkeypatch):
     """Deep-K launches with too few tiles for 256 CUs (the MiT spatial-reduction convs: 100 x B rows, K up to 4 096) contract K
     in slices by separate blocks + a deterministic reduce (ConvParams::splitk).  PF_SPLITK=0 disables it: same results up to
-    fp32 summation order, far inside the parity tolerances; and the split path itself is run-to-run deterministic."""
+    fp32 summation order, far inside the parity tolerances; and the split path itself is run-to-run deterministic.
+    The dispatch report is the witness that the switch acted (it is read per engine: once it was cached at first use, and this test compared the default engine with
+    itself): split-K launches in the default engine, none with PF_SPLITK=0."""
     from perspectivefields_amd import PerspectiveFields
 
     imgs = [synthetic_image(72, 96, seed=700 + i) for i in range(3)]
     base = model("centered").inference_batch(imgs)
     again = model("centered").inference_batch(imgs)
+    base_rep = model("centered")._get_engine().last_dispatch()
     monkeypatch.setenv("PF_SPLITK", "0")
-    alt = PerspectiveFields(CASES["centered"], weights="synthetic:0").eval().cuda().inference_batch(imgs)
+    alt_model = PerspectiveFields(CASES["centered"], weights="synthetic:0").eval().cuda()
+    alt = alt_model.inference_batch(imgs)
+    alt_rep = alt_model._get_engine().last_dispatch()
+    assert base_rep["batch"] == alt_rep["batch"] == 3 and base_rep["splitk_launches"] > 0 and base_rep["splitk_max_factor"] > 1, base_rep
+    assert alt_rep["splitk_launches"] == 0 and alt_rep["splitk_max_factor"] == 0 and alt_rep["conv_launches"] == base_rep["conv_launches"], alt_rep
     for a, b, c2 in zip(base, alt, again):
         assert torch.equal(a["pred_gravity"], c2["pred_gravity"]) and float(a["pred_roll"]) == float(c2["pred_roll"])
         c = one_minus_cos(a["pred_gravity"].cpu().numpy(), b["pred_gravity"].cpu().numpy()).max()
@@ -523,11 +543,16 @@ def test_row_block_forms_of_mit_stage3_agree(monkeypatch, mask):
     the CPU oracle on one image of the batch."""
     from perspectivefields_amd import PerspectiveFields
 
-    imgs = [synthetic_image(72, 96, seed=520 + (i % 5)) for i in range(32)]
+    imgs = [synthetic_image(72, 96, seed=520 + i) for i in range(32)]   # a distinct image per slot
     base = model("centered").inference_batch(imgs)
+    base_rep = model("centered")._get_engine().last_dispatch()
     monkeypatch.setenv("PF_RB_CHAIN", str(mask))
     alt_model = PerspectiveFields(CASES["centered"], weights="synthetic:0").eval().cuda()
     alt = alt_model.inference_batch(imgs)
+    alt_rep = alt_model._get_engine().last_dispatch()
+    # the dispatch report shows that the forms are live at this batch and that the mask changed them
+    assert base_rep["batch"] == alt_rep["batch"] == 32 and base_rep["rb_launches"] > 0 and alt_rep["rb_launches"] != base_rep["rb_launches"], (base_rep, alt_rep)
+    assert (alt_rep["rb_launches"] == 0) == (mask == 0) and alt_rep["fork_alloc_conflicts"] == 0, alt_rep
     for i in (0, 13, 31):
         a, b = base[i], alt[i]
         c = one_minus_cos(a["pred_gravity"].cpu().numpy(), b["pred_gravity"].cpu().numpy()).max()

@@ -226,10 +226,13 @@ def test_stage3_batch_split_is_bit_identical(monkeypatch):
         m = PerspectiveFields(CENTERED, weights="synthetic:0", precision="fp32").eval().cuda()
         eng = m._get_engine()
         pg, pl, pr = eng.forward(x)
+        rep = eng.last_dispatch()
+        assert rep["batch"] == 32 and rep["s3_split_taken"] == (1 if mode == "2" else 0) and rep["fork_alloc_conflicts"] == 0, (mode, rep)   # the split really ran / did not
         eng.set_defer_params(True)
         runs = [eng.forward(x) for _ in range(3)]
         eng.set_defer_params(False)
         torch.cuda.synchronize()
+        assert eng.last_dispatch()["s3_split_taken"] == rep["s3_split_taken"]
         for g2, l2, p2 in runs:
             assert torch.equal(g2, pg) and torch.equal(l2, pl) and torch.equal(p2, pr), mode
         outs[mode] = (pg, pl, pr)

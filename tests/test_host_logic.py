@@ -625,3 +625,56 @@ def test_verify_trained_script_without_weights(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(root, "scripts", "verify_trained.py")], capture_output=True, text=True, timeout=300, env=dict(env, PF_WEIGHTS_DIR=str(tmp_path)))
     # an (empty) weights directory: on a box without a GPU the script says so (2); on a GPU box every version is reported as "checkpoint not in PF_WEIGHTS_DIR" (0)
     assert (r.returncode == 2 and "no GPU visible" in r.stdout) or (r.returncode == 0 and "not in PF_WEIGHTS_DIR" in r.stdout), (r.returncode, r.stdout[-300:])
+
+
+# Engine configurations that change what the forward allocates from the workspace (tests/test_gpu_batch_dispatch.py runs the same list on the GPU with guard bands)
+WORKSPACE_CONFIGS = [{}, {"PF_FUSE_LN": "0"}, {"PF_RB_CHAIN": "0"}, {"PF_RB_CHAIN": "28"}, {"PF_SPLITK": "0"}, {"PF_SBA": "1"}, {"PF_FOLD_MLP": "0"}, {"PF_FUSE_UPSAMPLE": "0"}]
+
+
+def test_workspace_dry_run_for_every_batch_and_configuration(monkeypatch):
+    """The workspace dry run (a host-only engine, pf_create(PF_DEVICE_NONE), does it without a GPU) finishes for every batch 1..81, the three architectures, both
+    precision schemes and every configuration of WORKSPACE_CONFIGS, and its size never shrinks when the batch grows.  The batches at which the per-image step
+    changes are printed: each marks a batch gate that moves the peak.  (Seen: the steps into batch 4 and into batch 5 differ from their predecessors, i.e. ONE gate, at
+    batch 4, in the split-f16 scheme; none in the exact scheme or with PF_SBA=1.  The decoders' 320 x 320 maps set the peak, so the stage-3 gates at 16 / 28 / 32 /
+    64 do not show here: the GPU tests take those from the dispatch report, and run batch 4 as an edge of its own.)"""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from perspectivefields_amd.engine import load_library
+
+    lib = load_library()
+    PF_DEVICE_NONE = -1
+    engines = []
+    for version in ("Paramnet-360Cities-edina-centered", "Paramnet-360Cities-edina-uncentered", "PersNet-360Cities"):
+        sd = {k: (np.zeros((), dtype=np.float32) if k.endswith("num_batches_tracked") else np.ascontiguousarray(np.asarray(v), dtype=np.float32))
+              for k, v in synthetic_state_dict(version, 0).items()}
+        for cfg in WORKSPACE_CONFIGS:
+            with monkeypatch.context() as m:   # the switches are read by pf_create
+                for k, v in cfg.items():
+                    m.setenv(k, v)
+                h = ctypes.c_void_p()
+                assert lib.pf_create(ctypes.byref(h), PF_DEVICE_NONE, arch_of(get_cfg(version))["arch_id"]) == 0, lib.pf_last_error(None)
+            for key, arr in sd.items():
+                shape = (ctypes.c_int64 * max(arr.ndim, 1))(*arr.shape)
+                assert lib.pf_load_tensor(h, key.encode(), arr.ctypes.data_as(ctypes.c_void_p), shape, arr.ndim) == 0, lib.pf_last_error(h)
+            engines.append((version, cfg, h))
+    try:
+        with ThreadPoolExecutor(max_workers=8) as pool:   # the weight folds / splits of the engines are independent (ctypes releases the GIL)
+            rcs = list(pool.map(lambda e: lib.pf_finalize_weights(e[2]), engines))
+        for (version, cfg, h), rc in zip(engines, rcs):
+            assert rc == 0, (version, cfg, lib.pf_last_error(h))
+            for precision, mode in (("fp32", 0), ("fp32_bf16x6", 3)):
+                assert lib.pf_set_precision(h, mode) == 0, lib.pf_last_error(h)
+                ws = [int(lib.pf_workspace_bytes(h, b)) for b in range(1, 82)]
+                what = f"{version} {cfg or 'default'} {precision}"
+                assert all(w > 0 for w in ws), what
+                assert all(b >= a for a, b in zip(ws, ws[1:])), f"{what}: workspace_bytes shrinks with the batch: {ws}"
+                assert int(lib.pf_workspace_bytes(h, 82)) == 0, what   # beyond PF_MAX_BATCH
+                steps = [b - a for a, b in zip(ws, ws[1:])]
+                edges = [b + 2 for b in range(1, len(steps)) if steps[b] != steps[b - 1]]
+                print(f"{what}: B=1 {ws[0]} bytes, B=81 {ws[-1]} bytes, per-image step changes at batches {edges}")
+            out = (ctypes.c_int64 * 32)()
+            assert lib.pf_last_dispatch(h, out, 32) == 0 and not any(out), "a dry run must not touch the dispatch report"
+            assert lib.pf_last_dispatch(h, out, 3) != 0   # too short an array is refused
+    finally:
+        for _, _, h in engines:
+            lib.pf_destroy(h)
