@@ -346,6 +346,53 @@ int pf_pano_crop(int device, int n_pano, const void* const* h_pano, const int32_
                  const int32_t* h_pano_index /*[batch]*/, const float* d_cam7 /*[batch][7]*/, int H, int W,
                  void* d_img /*[batch][H][W][3], dtype*/, float* d_up /*[batch][2][H][W]*/, float* d_lat /*[batch][H][W]*/, void* stream);
 
+/* Predicted perspective fields against ground truth on the device: per-pixel errors, per-image statistics with an exact median, and
+ * a running histogram for dataset statistics (field_err.hip).
+ * Inputs per image: up_pred, up_gt [2][H][W] and lat_pred, lat_gt [H][W] degrees, fp32 (the layout of pred_gravity_original /
+ * pred_latitude_original and of pf_pano_crop's labels).  With p = up_pred, g = up_gt at one pixel:
+ *   e_up  = atan2(|p_x g_y - p_y g_x|, p_x g_x + p_y g_y) in degrees, in [0, 180] (cross and dot, no normalisation, no acos)
+ *   e_lat = |lat_pred - lat_gt| in degrees
+ *   valid   all six input values finite and both vectors of squared length >= 1e-12 (and the fp32 cross, dot and difference finite: components
+ *           beyond ~1e19 count as non-finite).  A caller masks a pixel by writing NaN into the label; pf_pano_crop's NaN labels mask themselves.
+ *           Invalid pixels enter no statistic.
+ * Per image and per metric over the n valid pixels: mean, rmse, max, median, frac_below (share with e < threshold_deg, strict) and n.  The
+ * median is numpy's: with the errors sorted, (s[(n-1)/2] + s[n/2]) / 2, both order statistics exact elements of the fp32 error set (radix
+ * selection on the bit patterns, which order like unsigned integers for non-negative floats), their average taken in fp64.  n = 0: NaN
+ * statistics and n = 0, not an error.  Sums are reduced in fp64 in a fixed order and counts are integers: deterministic, each image's row
+ * independent of the batch it is in.
+ * h_hw = HOST [B][2] (H, W), each >= 1, H * W < 2^31; h_* = HOST arrays of B DEVICE pointers.  d_out = DEVICE [B][PF_FERR_COLS] fp64 (columns
+ * below) or NULL.  h_err_up / h_err_lat: optional per-pixel error maps [H][W], NaN where invalid; both or neither.
+ * d_hist = optional DEVICE [2][PF_FERR_BINS] int64 running histogram (up, lat), ADDED to: bins of 1 / PF_FERR_BINS_PER_DEG degree,
+ * bin = min((int)(e * 64), PF_FERR_BINS - 1) (e * 64 is exact in fp32: the bin of an fp32 error is the same everywhere; errors >= 180 land in
+ * the last bin).  d_hist_sums (required with d_hist, else NULL) = DEVICE [2][PF_FERR_SUMS] fp64 running totals per metric, columns
+ * PF_FERR_SUM_*; a zeroed pair is an empty state, states merge by addition (the maximum by max).
+ * threshold_deg finite and > 0.  Workspace: pf_field_errors_workspace_bytes(B, h_hw) (0 for bad sizes).  Argument errors return PF_ERR_ARG
+ * before any device work.  Everything is enqueued on `stream`, no host synchronisation; stateless, no handle. */
+#define PF_FERR_COL_UP_MEAN 0
+#define PF_FERR_COL_UP_MEDIAN 1
+#define PF_FERR_COL_UP_RMSE 2
+#define PF_FERR_COL_UP_MAX 3
+#define PF_FERR_COL_UP_FRAC_BELOW 4
+#define PF_FERR_COL_LAT_MEAN 5
+#define PF_FERR_COL_LAT_MEDIAN 6
+#define PF_FERR_COL_LAT_RMSE 7
+#define PF_FERR_COL_LAT_MAX 8
+#define PF_FERR_COL_LAT_FRAC_BELOW 9
+#define PF_FERR_COL_VALID_PIXELS 10
+#define PF_FERR_COLS 11
+#define PF_FERR_BINS 11520
+#define PF_FERR_BINS_PER_DEG 64
+#define PF_FERR_SUM_N 0        /* valid pixels */
+#define PF_FERR_SUM_E 1        /* sum of the errors */
+#define PF_FERR_SUM_E2 2       /* sum of their squares */
+#define PF_FERR_SUM_MAX 3      /* largest error (0 for an empty state) */
+#define PF_FERR_SUM_BELOW 4    /* errors < threshold_deg */
+#define PF_FERR_SUMS 5
+size_t pf_field_errors_workspace_bytes(int batch, const int32_t* h_hw);
+int pf_field_errors(int device, int batch, const int32_t* h_hw, const float* const* h_up_pred, const float* const* h_lat_pred,
+                    const float* const* h_up_gt, const float* const* h_lat_gt, float threshold_deg, double* d_out, float* const* h_err_up,
+                    float* const* h_err_lat, int64_t* d_hist, double* d_hist_sums, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- kernel-level entry points (used by the parity tests; same kernels pf_forward runs) ----
  * NHWC fp32 device activations; weights are HOST pointers in the reference's layouts.
  * "planes": the engine's internal split activation formats -- an fp32 tensor stored as planes of 16-bit values, plane k at

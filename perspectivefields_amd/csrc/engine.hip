@@ -2171,6 +2171,78 @@ int pf_fit_camera(int device, int B, const int32_t* hw, const float* const* up, 
   return PF_OK;
 }
 
+// workspace of pf_field_errors: per-image selection state, output rows (used when d_out is NULL), the level histograms of every image (one
+// region, zeroed per call), then per image the partial records and the two error maps (used unless the caller gives maps); 256-byte aligned
+static size_t ferr_align(size_t n) { return (n + 255) & ~(size_t)255; }
+static size_t ferr_hist_bytes() { return (size_t)3 * FERR_SEL * FERR_LEVEL_BINS * sizeof(unsigned); }
+static size_t ferr_part_bytes(int H, int W) { return ferr_align((size_t)ferr_blocks_per_image(H, W) * FERR_REC * sizeof(double)); }
+static size_t ferr_map_bytes(int H, int W) { return ferr_align((size_t)H * W * sizeof(float)); }
+static bool ferr_size_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1LL << 31); }
+
+size_t pf_field_errors_workspace_bytes(int B, const int32_t* hw) {
+  if (B <= 0 || !hw) return 0;
+  size_t n = 256 + ferr_align((size_t)B * sizeof(FerrState)) + ferr_align((size_t)B * PF_FERR_COLS * sizeof(double)) + (size_t)B * ferr_hist_bytes();
+  for (int i = 0; i < B; ++i) {
+    if (!ferr_size_ok(hw[2 * i], hw[2 * i + 1])) return 0;
+    n += ferr_part_bytes(hw[2 * i], hw[2 * i + 1]) + 2 * ferr_map_bytes(hw[2 * i], hw[2 * i + 1]);
+  }
+  return n;
+}
+
+int pf_field_errors(int device, int B, const int32_t* hw, const float* const* up_pred, const float* const* lat_pred, const float* const* up_gt,
+                    const float* const* lat_gt, float threshold_deg, double* d_out, float* const* err_up, float* const* err_lat, int64_t* d_hist,
+                    double* d_hist_sums, void* ws, size_t ws_bytes, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_field_errors: " + m; return PF_ERR_ARG; };
+  if (B <= 0 || !hw || !up_pred || !lat_pred || !up_gt || !lat_gt) return bad("batch >= 1, h_hw and the four field pointer arrays are required");
+  if (!(threshold_deg > 0.f && std::isfinite(threshold_deg))) return bad("threshold_deg must be finite and > 0");
+  if (!err_up != !err_lat) return bad("h_err_up and h_err_lat are both given or both NULL");
+  if (!d_hist != !d_hist_sums) return bad("d_hist and d_hist_sums are both given or both NULL");
+  for (int i = 0; i < B; ++i) {
+    if (!ferr_size_ok(hw[2 * i], hw[2 * i + 1])) return bad(fmt("image %d is %d x %d", i, hw[2 * i], hw[2 * i + 1]));
+    if (!up_pred[i] || !lat_pred[i] || !up_gt[i] || !lat_gt[i]) return bad(fmt("NULL field pointer of image %d", i));
+    if (err_up && (!err_up[i] || !err_lat[i])) return bad(fmt("NULL error-map pointer of image %d", i));
+  }
+  const size_t need = pf_field_errors_workspace_bytes(B, hw);
+  if (!ws || ws_bytes < need) { g_create_error = fmt("pf_field_errors: needs %zu workspace bytes, got %zu", need, ws_bytes); return PF_ERR_WORKSPACE; }
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+  FerrState* state = reinterpret_cast<FerrState*>(p);
+  p += ferr_align((size_t)B * sizeof(FerrState));
+  double* rows = d_out ? d_out : reinterpret_cast<double*>(p);
+  p += ferr_align((size_t)B * PF_FERR_COLS * sizeof(double));
+  char* hist = p;
+  p += (size_t)B * ferr_hist_bytes();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(hist, 0, (size_t)B * ferr_hist_bytes(), s) != hipSuccess) { g_create_error = "pf_field_errors: hipMemsetAsync failed"; return PF_ERR_DEVICE; }
+  for (int i0 = 0; i0 < B; i0 += FerrBatch::MAX) {
+    FerrBatch fb;
+    fb.n = std::min(B - i0, (int)FerrBatch::MAX);
+    for (int k = 0; k < fb.n; ++k) {
+      const int i = i0 + k, H = hw[2 * i], W = hw[2 * i + 1];
+      fb.H[k] = H; fb.W[k] = W; fb.nblk[k] = ferr_blocks_per_image(H, W);
+      fb.up_pred[k] = up_pred[i]; fb.lat_pred[k] = lat_pred[i]; fb.up_gt[k] = up_gt[i]; fb.lat_gt[k] = lat_gt[i];
+      fb.part[k] = reinterpret_cast<double*>(p);
+      p += ferr_part_bytes(H, W);
+      fb.err_up[k] = err_up ? err_up[i] : reinterpret_cast<float*>(p);
+      fb.err_lat[k] = err_up ? err_lat[i] : reinterpret_cast<float*>(p + ferr_map_bytes(H, W));
+      p += 2 * ferr_map_bytes(H, W);
+      fb.hist[k] = reinterpret_cast<unsigned*>(hist + (size_t)i * ferr_hist_bytes());
+      const uintptr_t align = reinterpret_cast<uintptr_t>(up_pred[i]) | reinterpret_cast<uintptr_t>(lat_pred[i]) | reinterpret_cast<uintptr_t>(up_gt[i]) |
+                              reinterpret_cast<uintptr_t>(lat_gt[i]) | reinterpret_cast<uintptr_t>(fb.err_up[k]) | reinterpret_cast<uintptr_t>(fb.err_lat[k]);
+      fb.vec[k] = (((size_t)H * W) % 4 == 0 && (align & 15) == 0) ? 1 : 0;  // H * W % 4: the second up plane starts at up + H * W
+    }
+    fb.state = state + i0;
+    fb.out = rows + (size_t)i0 * PF_FERR_COLS;
+    fb.threshold = threshold_deg;
+    launch_field_errors(fb, s);
+    if (d_hist) launch_field_errors_hist(fb, reinterpret_cast<long long*>(d_hist), d_hist_sums, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_field_errors: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
 int pf_profile_begin(pf_handle h, unsigned class_mask) {
   if (!h) return PF_ERR_ARG;
   h->prof.reset();

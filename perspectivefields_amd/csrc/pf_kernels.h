@@ -410,4 +410,35 @@ struct PanoBatch {
 };
 void launch_pano_crop(const PanoBatch& pb, int dtype, hipStream_t s);
 
+// predicted fields against ground truth (field_err.hip, include/pf_hip.h pf_field_errors): up to FerrBatch::MAX images per launch,
+// per-image sizes and pointers in the kernel arguments
+constexpr int FERR_REC = 10;         // doubles of one accumulate block's partial record
+constexpr int FERR_LEVEL_BINS = 2048;  // bins of one radix level (11 bits; the last level uses 512 of them)
+constexpr int FERR_SEL = 4;          // selections per image: ranks (n - 1) / 2 and n / 2 of e_up, then of e_lat
+struct FerrState {                   // per image, written by the pick kernels
+  double sums[2][5];                 // per metric, the PF_FERR_SUM_* columns
+  unsigned long long rank[FERR_SEL]; // rank of the wanted element among those that share `prefix`
+  unsigned prefix[FERR_SEL];         // the bits of the wanted element found so far
+};
+struct FerrBatch {
+  static constexpr int MAX = 32;
+  int n;
+  int H[MAX], W[MAX], nblk[MAX];
+  int vec[MAX];                 // 1: H * W % 4 == 0 and every plane 16-byte aligned: 16-byte loads and stores
+  const float* up_pred[MAX];    // [2][H][W]
+  const float* lat_pred[MAX];   // [H][W] degrees
+  const float* up_gt[MAX];
+  const float* lat_gt[MAX];
+  float* err_up[MAX];           // [H][W] error maps (the caller's or the workspace's), NaN where invalid
+  float* err_lat[MAX];
+  double* part[MAX];            // [nblk][FERR_REC]
+  unsigned* hist[MAX];          // [3 levels][FERR_SEL][FERR_LEVEL_BINS], zeroed before the first launch
+  FerrState* state;             // [n]
+  double* out;                  // [n][PF_FERR_COLS]
+  float threshold;
+};
+int ferr_blocks_per_image(int H, int W);
+void launch_field_errors(const FerrBatch& fb, hipStream_t s);  // accumulate + three (histogram, pick) levels
+void launch_field_errors_hist(const FerrBatch& fb, long long* d_hist, double* d_hist_sums, hipStream_t s);  // after launch_field_errors
+
 }  // namespace pf

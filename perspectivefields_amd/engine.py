@@ -63,6 +63,8 @@ _SIGNATURES = {
     "pf_fit_camera_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
     "pf_fit_camera": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_int, _P, _P, _c.c_size_t, _P]),
     "pf_pano_crop": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P]),
+    "pf_field_errors_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
+    "pf_field_errors": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_float, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
     "pf_profile_begin": (_c.c_int, [_P, _c.c_uint]),
     "pf_profile_pause": (_c.c_int, [_P]),
     "pf_profile_end": (_c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_long), _c.c_int]),

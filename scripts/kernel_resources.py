@@ -145,9 +145,16 @@ if __name__ == "__main__":
         diff = compare(sys.argv[2], new)
         print("\n".join(diff) if diff else "no kernel changed its spills or its resident blocks per CU")
         sys.exit(0)
+    only = None
+    if "--filter" in sys.argv:  # kernel_resources.py --filter ferr_ [LIB.so]: the kernels whose name contains the text (the tables of DESIGN.md sections 10, 11, 13)
+        i = sys.argv.index("--filter")
+        only = sys.argv[i + 1]
+        del sys.argv[i:i + 2]
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "perspectivefields_amd", "lib", "libpf_hip.so")
     rows = kernels(lib)
-    print(f"{len(rows)} gfx950 kernels in {os.path.relpath(lib, ROOT)}")
+    if only:
+        rows = [r for r in rows if only in r["kernel"]]
+    print(f"{len(rows)} gfx950 kernels in {os.path.relpath(lib, ROOT)}" + (f" matching '{only}'" if only else ""))
     print(f"{'vgpr':>5} {'spill':>5} {'scratch':>7} {'lds':>7} {'thr':>5} {'blk/CU':>6}  kernel")
     for r in rows:
         print(f"{r['vgpr']:5d} {r['spill']:5d} {r['scratch']:7d} {r['lds']:7d} {r['max_threads']:5d} {blocks_per_cu(r):6d}  {r['kernel']}")

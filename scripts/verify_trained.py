@@ -125,6 +125,11 @@ def main(argv=None):
         row(version, f"fp32 (split-f16) vs fp32_bf16x6 on {len(imgs)} images: 1-cos / lat L1 / scalars", f"{worst[0]:.2e} / {worst[1]:.2e} deg / {worst[2]:.2e}",
             worst[0] <= TOL["up_1_minus_cos"] and worst[1] <= TOL["latitude_l1_deg"] and (worst[2] <= TOL["paramnet"] or not m_fast.param_on))
         row(version, "saturation counter moved by the fast-mode run", str(moved), moved == 0)
+        # extra line, no check: the same comparison through field_errors (per-pixel angles, the exact-mode fields as the label)
+        p_fast, p_exact = m_fast.inference_batch(imgs), m_exact.inference_batch(imgs)
+        fe = m_fast.field_errors(p_fast, [p["pred_gravity_original"] for p in p_exact], [p["pred_latitude_original"] for p in p_exact])
+        row(version, "fp32 vs fp32_bf16x6 fields (field_errors): worst up / latitude max, worst median", f"{max(float(d['up_max_deg']) for d in fe):.2e} / "
+            f"{max(float(d['lat_max_deg']) for d in fe):.2e} deg, {max(float(d['up_median_deg']) for d in fe):.2e} / {max(float(d['lat_median_deg']) for d in fe):.2e} deg", None)
         # 5: the unmodified reference on CPU, same checkpoint
         try:
             sys.path.insert(0, ROOT)
