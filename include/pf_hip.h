@@ -315,6 +315,51 @@ int pf_fit_camera(int device, int batch, const int32_t* h_hw, const float* const
                   int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* d_workspace,
                   size_t workspace_bytes, void* stream);
 
+/* The same fit for the Unified Spherical Model (USM): the mirror parameter xi of pf_pano_crop's distorted views is one more unknown
+ * (DESIGN.md section 14).  theta = (roll r, pitch p, f, cx, cy, xi).  free_pp = 0: 4 free parameters (r, p, f, xi), cx / cy held at their
+ * start values (0 without d_init); 1: all 6 free.  THE MODEL -- pf_pano_crop's intrinsics, ray, rotation and label formulas; yaw does not enter:
+ *   F = f*H, Cx = (cx + 1/2)*W, Cy = (cy + 1/2)*H
+ *   image point (a, b) -> x = (a - Cx)/F, y = (b - Cy)/F, rho^2 = x^2 + y^2, disc = 1 + (1 - xi^2) rho^2, eta = (xi + sqrt(disc)) / (1 + rho^2),
+ *       X = (eta x, eta y, eta - xi), X_w = R_pitch(p) R_roll(r) X
+ *   up at (col + 1/2, row + 1/2): with g = R^T (0, -1, 0), D = X_z + xi, s = g_z + xi (X . g): (g_x D - X_x s, g_y D - X_y s) normalised
+ *   lat in degrees: that of X_w at the linspace point (col W/(W-1), row H/(H-1))
+ *   a pixel with disc < 0 at either point has no model value: weight 0, not counted in VALID_PIXELS
+ * At xi = 0 this is the pinhole model of pf_fit_camera.  Residuals, loss, weights, accept / reject rule, damping and stopping rule: as pf_fit_camera.
+ * Clamps: |pitch| <= 89.9 deg, f >= 1e-3, xi in [-0.5, 2] (negative on purpose: a pinhole truth is an interior point); roll is kept in
+ * [-pi, pi] (it is periodic, and a long early step of the 6-parameter fit may land whole turns away).
+ * Start: d_init = NULL -> roll / pitch from the fields at the image centre (the centre ray is (0, 0, 1) for every xi), xi = 0 and f from the
+ * 16-candidate vFoV search; else d_init = DEVICE [B][6] theta (angles in radians).  xi > 1 leaves part of the image without a ray, a region
+ * that moves with the parameters: such cameras are supported from a caller-supplied start, not promised from the blind one.
+ * d_out = DEVICE [B][PF_USMFIT_COLS] fp32: the thirteen columns of pf_fit_camera in the same order, then xi.  VFOV and GENERAL_VFOV keep
+ * their formulas in f, cx, cy: under xi != 0 they describe the intrinsics, not the angle the image subtends.
+ * Sizes, pointers, argument checks (PF_ERR_ARG before any device work), launches (max_iter + 1 pairs per 32 images on `stream`, no host
+ * synchronisation) and determinism (an image's bits do not depend on its batch) as pf_fit_camera; workspace pf_fit_camera_usm_workspace_bytes
+ * (0 for batch <= 0 or a size below 8). */
+#define PF_USMFIT_COL_ROLL 0
+#define PF_USMFIT_COL_PITCH 1
+#define PF_USMFIT_COL_VFOV 2
+#define PF_USMFIT_COL_REL_FOCAL 3
+#define PF_USMFIT_COL_GENERAL_VFOV 4
+#define PF_USMFIT_COL_REL_CX 5
+#define PF_USMFIT_COL_REL_CY 6
+#define PF_USMFIT_COL_RMS_UP 7
+#define PF_USMFIT_COL_RMS_LAT 8
+#define PF_USMFIT_COL_COST 9
+#define PF_USMFIT_COL_ITERATIONS 10
+#define PF_USMFIT_COL_CONVERGED 11
+#define PF_USMFIT_COL_VALID_PIXELS 12 /* pixels with finite input and a ray */
+#define PF_USMFIT_COL_XI 13
+#define PF_USMFIT_COLS 14
+size_t pf_fit_camera_usm_workspace_bytes(int batch, const int32_t* h_hw);
+int pf_fit_camera_usm(int device, int batch, const int32_t* h_hw, const float* const* h_up, const float* const* h_lat,
+                      const float* d_init /* NULL or [B][6] */, int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat,
+                      int max_iter, float* d_out /* [B][PF_USMFIT_COLS] */, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* The forward direction of that model: d_cam6 = {roll, pitch (RADIANS), rel_focal, rel_cx, rel_cy, xi} in device memory -> d_up [2][H][W],
+ * d_lat [H][W] degrees; NaN where a point has no ray (xi > 1).  xi == 0 gives the bits of pf_fields_from_params; otherwise pf_pano_crop's
+ * label formulas.  xi is read on the device, so a fitted xi feeds it without a host round trip.  Stateless, no handle. */
+int pf_fields_from_params_usm(int device, const float* d_cam6, int H, int W, float* d_up, float* d_lat, void* stream);
+
 /* Equirectangular panoramas -> camera views and their ground-truth perspective fields on the device: the reference's labelled-data
  * tooling, PanoCam.get_image / crop_equi (utils/panocam.py:132-249), crop_distortion (:558-752, Unified Spherical Model) and
  * get_up_general / get_lat_general (:451-556).  DESIGN.md section 11.

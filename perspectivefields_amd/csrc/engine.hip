@@ -2107,44 +2107,54 @@ int pf_pano_crop(int device, int n_pano, const void* const* pano, const int32_t*
   return PF_OK;
 }
 
-// workspace of pf_fit_camera: per-image LM state, then every image's partial records, each region 256-byte aligned
-static size_t fit_state_bytes(int B) { return ((size_t)B * FIT_STATE * sizeof(double) + 255) & ~(size_t)255; }
-static size_t fit_part_bytes(int H, int W) { return ((size_t)fit_blocks_per_image(H, W) * FIT_REC * sizeof(double) + 255) & ~(size_t)255; }
+// workspace of pf_fit_camera / pf_fit_camera_usm: per-image LM state, then every image's partial records, each region 256-byte aligned.
+// The two fits differ in their state, record, start and output row sizes and in their kernels only.
+struct FitKind {
+  const char* name;
+  int state, rec, ntheta, cols;
+  void (*init)(const FitBatch&, const FitParams&, hipStream_t);
+  void (*iteration)(const FitBatch&, const FitParams&, hipStream_t);
+};
+static const FitKind kFitPinhole{"pf_fit_camera", FIT_STATE, FIT_REC, 5, PF_FIT_COLS, launch_fit_init, launch_fit_iteration};
+static const FitKind kFitUsm{"pf_fit_camera_usm", USMFIT_STATE, USMFIT_REC, 6, PF_USMFIT_COLS, launch_usmfit_init, launch_usmfit_iteration};
+static size_t fit_state_bytes(const FitKind& fk, int B) { return ((size_t)B * fk.state * sizeof(double) + 255) & ~(size_t)255; }
+static size_t fit_part_bytes(const FitKind& fk, int H, int W) { return ((size_t)fit_blocks_per_image(H, W) * fk.rec * sizeof(double) + 255) & ~(size_t)255; }
 
-size_t pf_fit_camera_workspace_bytes(int B, const int32_t* hw) {
+static size_t fit_workspace_bytes(const FitKind& fk, int B, const int32_t* hw) {
   if (B <= 0 || !hw) return 0;
-  size_t n = 256 + fit_state_bytes(B);  // + 256: alignment of the caller's pointer
+  size_t n = 256 + fit_state_bytes(fk, B);  // + 256: alignment of the caller's pointer
   for (int i = 0; i < B; ++i) {
     if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) return 0;
-    n += fit_part_bytes(hw[2 * i], hw[2 * i + 1]);
+    n += fit_part_bytes(fk, hw[2 * i], hw[2 * i + 1]);
   }
   return n;
 }
 
-int pf_fit_camera(int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int loss,
-                  float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes, void* stream) {
-  std::string err;
-  int rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  if (B <= 0 || !hw || !up || !lat || !d_out) { g_create_error = "pf_fit_camera: bad argument"; return PF_ERR_ARG; }
+static int fit_camera_run(const FitKind& fk, int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init,
+                          int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes,
+                          void* stream) {
+  if (B <= 0 || !hw || !up || !lat || !d_out) { g_create_error = fmt("%s: bad argument", fk.name); return PF_ERR_ARG; }
   if ((free_pp != 0 && free_pp != 1) || (loss != PF_FIT_LOSS_L2 && loss != PF_FIT_LOSS_HUBER) || max_iter < 1 || max_iter > 1000) {
-    g_create_error = fmt("pf_fit_camera: bad option (free_pp %d, loss %d, max_iter %d)", free_pp, loss, max_iter);
+    g_create_error = fmt("%s: bad option (free_pp %d, loss %d, max_iter %d)", fk.name, free_pp, loss, max_iter);
     return PF_ERR_ARG;
   }
   if (!(w_up >= 0.f && w_lat >= 0.f && std::isfinite(w_up) && std::isfinite(w_lat) && w_up + w_lat > 0.f) ||
       (loss == PF_FIT_LOSS_HUBER && !(huber_delta_deg > 0.f && std::isfinite(huber_delta_deg)))) {
-    g_create_error = "pf_fit_camera: weights must be finite, >= 0 and not both 0; huber_delta_deg must be finite and > 0";
+    g_create_error = fmt("%s: weights must be finite, >= 0 and not both 0; huber_delta_deg must be finite and > 0", fk.name);
     return PF_ERR_ARG;
   }
   for (int i = 0; i < B; ++i) {
-    if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) { g_create_error = fmt("pf_fit_camera: image %d is %d x %d, smaller than 8 x 8", i, hw[2 * i], hw[2 * i + 1]); return PF_ERR_ARG; }
-    if (!up[i] || !lat[i]) { g_create_error = fmt("pf_fit_camera: NULL field pointer of image %d", i); return PF_ERR_ARG; }
+    if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) { g_create_error = fmt("%s: image %d is %d x %d, smaller than 8 x 8", fk.name, i, hw[2 * i], hw[2 * i + 1]); return PF_ERR_ARG; }
+    if (!up[i] || !lat[i]) { g_create_error = fmt("%s: NULL field pointer of image %d", fk.name, i); return PF_ERR_ARG; }
   }
-  const size_t need = pf_fit_camera_workspace_bytes(B, hw);
-  if (!ws || ws_bytes < need) { g_create_error = fmt("pf_fit_camera: needs %zu workspace bytes, got %zu", need, ws_bytes); return PF_ERR_WORKSPACE; }
+  const size_t need = fit_workspace_bytes(fk, B, hw);
+  if (!ws || ws_bytes < need) { g_create_error = fmt("%s: needs %zu workspace bytes, got %zu", fk.name, need, ws_bytes); return PF_ERR_WORKSPACE; }
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
   char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
   double* state = reinterpret_cast<double*>(base);
-  char* part = base + fit_state_bytes(B);
+  char* part = base + fit_state_bytes(fk, B);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat};
   std::vector<FitBatch> groups;
@@ -2156,18 +2166,42 @@ int pf_fit_camera(int device, int B, const int32_t* hw, const float* const* up, 
       fb.H[k] = H; fb.W[k] = W; fb.nblk[k] = fit_blocks_per_image(H, W);
       fb.up[k] = up[i]; fb.lat[k] = lat[i];
       fb.part[k] = reinterpret_cast<double*>(part);
-      part += fit_part_bytes(H, W);
+      part += fit_part_bytes(fk, H, W);
     }
-    fb.state = state + (size_t)i0 * FIT_STATE;
-    fb.out = d_out + (size_t)i0 * PF_FIT_COLS;
-    fb.init = d_init ? d_init + (size_t)i0 * 5 : nullptr;
+    fb.state = state + (size_t)i0 * fk.state;
+    fb.out = d_out + (size_t)i0 * fk.cols;
+    fb.init = d_init ? d_init + (size_t)i0 * fk.ntheta : nullptr;
     groups.push_back(fb);
   }
   // no host synchronisation: every image stops on its own flag, the launches run out as no-ops
-  for (const FitBatch& fb : groups) launch_fit_init(fb, prm, s);
+  for (const FitBatch& fb : groups) fk.init(fb, prm, s);
   for (int it = 0; it <= max_iter; ++it)
-    for (const FitBatch& fb : groups) launch_fit_iteration(fb, prm, s);
-  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_fit_camera: kernel launch failed"; return PF_ERR_DEVICE; }
+    for (const FitBatch& fb : groups) fk.iteration(fb, prm, s);
+  if (hipGetLastError() != hipSuccess) { g_create_error = fmt("%s: kernel launch failed", fk.name); return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+size_t pf_fit_camera_workspace_bytes(int B, const int32_t* hw) { return fit_workspace_bytes(kFitPinhole, B, hw); }
+
+int pf_fit_camera(int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int loss,
+                  float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes, void* stream) {
+  return fit_camera_run(kFitPinhole, device, B, hw, up, lat, d_init, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out, ws, ws_bytes, stream);
+}
+
+size_t pf_fit_camera_usm_workspace_bytes(int B, const int32_t* hw) { return fit_workspace_bytes(kFitUsm, B, hw); }
+
+int pf_fit_camera_usm(int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int loss,
+                      float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes, void* stream) {
+  return fit_camera_run(kFitUsm, device, B, hw, up, lat, d_init, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out, ws, ws_bytes, stream);
+}
+
+int pf_fields_from_params_usm(int device, const float* d_cam6, int H, int W, float* d_up, float* d_lat, void* stream) {
+  if (!d_cam6 || !d_up || !d_lat || H <= 0 || W <= 0) { g_create_error = "pf_fields_from_params_usm: bad argument"; return PF_ERR_ARG; }
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  launch_fields_usm(d_cam6, H, W, d_up, d_lat, static_cast<hipStream_t>(stream));
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_fields_from_params_usm: kernel launch failed"; return PF_ERR_DEVICE; }
   return PF_OK;
 }
 

@@ -11,147 +11,12 @@
 #include <algorithm>
 
 #include "../../include/pf_hip.h"
+#include "fit_dual.h"
 #include "pf_kernels.h"
 
 namespace pf {
 
 namespace {
-
-constexpr float kRad2Deg = 57.29577951308232f;
-
-// ---------------------------------------------------------------- forward-mode dual numbers, N derivatives
-template <int N>
-struct Dual {
-  float v;
-  float d[N];
-};
-template <int N>
-__device__ __forceinline__ Dual<N> dconst(float v) {
-  Dual<N> r;
-  r.v = v;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = 0.f;
-  return r;
-}
-template <int N>
-__device__ __forceinline__ Dual<N> dvar(float v, int k0) {
-  Dual<N> r = dconst<N>(v);
-  if (k0 < N) r.d[k0] = 1.f;
-  return r;
-}
-template <int N>
-__device__ __forceinline__ Dual<N> operator+(const Dual<N>& a, const Dual<N>& b) {
-  Dual<N> r;
-  r.v = a.v + b.v;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = a.d[k] + b.d[k];
-  return r;
-}
-template <int N>
-__device__ __forceinline__ Dual<N> operator-(const Dual<N>& a, const Dual<N>& b) {
-  Dual<N> r;
-  r.v = a.v - b.v;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = a.d[k] - b.d[k];
-  return r;
-}
-template <int N>
-__device__ __forceinline__ Dual<N> operator-(const Dual<N>& a) {
-  Dual<N> r;
-  r.v = -a.v;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = -a.d[k];
-  return r;
-}
-template <int N>
-__device__ __forceinline__ Dual<N> operator*(const Dual<N>& a, const Dual<N>& b) {
-  Dual<N> r;
-  r.v = a.v * b.v;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = fmaf(a.v, b.d[k], a.d[k] * b.v);
-  return r;
-}
-template <int N>
-__device__ __forceinline__ Dual<N> operator*(const Dual<N>& a, float s) {
-  Dual<N> r;
-  r.v = a.v * s;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = a.d[k] * s;
-  return r;
-}
-template <int N>
-__device__ __forceinline__ Dual<N> operator+(const Dual<N>& a, float s) {
-  Dual<N> r = a;
-  r.v += s;
-  return r;
-}
-// a * s + b for a float s: the per-pixel affine forms
-template <int N>
-__device__ __forceinline__ Dual<N> fma_s(const Dual<N>& a, float s, const Dual<N>& b) {
-  Dual<N> r;
-  r.v = fmaf(a.v, s, b.v);
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = fmaf(a.d[k], s, b.d[k]);
-  return r;
-}
-__device__ __forceinline__ float fma_s(float a, float s, float b) { return fmaf(a, s, b); }
-template <int N>
-__device__ __forceinline__ Dual<N> recip(const Dual<N>& a) {
-  Dual<N> r;
-  r.v = 1.0f / a.v;
-  const float g = -r.v * r.v;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = a.d[k] * g;
-  return r;
-}
-__device__ __forceinline__ float recip(float a) { return 1.0f / a; }
-template <int N>
-__device__ __forceinline__ Dual<N> dsqrt(const Dual<N>& a) {
-  Dual<N> r;
-  r.v = sqrtf(a.v);
-  const float g = 0.5f / r.v;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = a.d[k] * g;
-  return r;
-}
-__device__ __forceinline__ float dsqrt(float a) { return sqrtf(a); }
-template <int N>
-__device__ __forceinline__ Dual<N> drsqrt(const Dual<N>& a) {
-  Dual<N> r;
-  r.v = 1.0f / sqrtf(a.v);
-  const float g = -0.5f * r.v * r.v * r.v;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = a.d[k] * g;
-  return r;
-}
-__device__ __forceinline__ float drsqrt(float a) { return 1.0f / sqrtf(a); }
-template <int N>
-__device__ __forceinline__ Dual<N> datan2(const Dual<N>& y, const Dual<N>& x) {
-  Dual<N> r;
-  r.v = atan2f(y.v, x.v);
-  const float q = 1.0f / (x.v * x.v + y.v * y.v);
-  const float gy = x.v * q, gx = -y.v * q;
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = fmaf(gy, y.d[k], gx * x.d[k]);
-  return r;
-}
-__device__ __forceinline__ float datan2(float y, float x) { return atan2f(y, x); }
-template <int N>
-__device__ __forceinline__ void dsincos(const Dual<N>& a, Dual<N>* s, Dual<N>* c) {
-  float sv, cv;
-  sincosf(a.v, &sv, &cv);
-  s->v = sv;
-  c->v = cv;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    s->d[k] = cv * a.d[k];
-    c->d[k] = -sv * a.d[k];
-  }
-}
-__device__ __forceinline__ void dsincos(float a, float* s, float* c) { sincosf(a, s, c); }
-__device__ __forceinline__ float val(float a) { return a; }
-template <int N>
-__device__ __forceinline__ float val(const Dual<N>& a) { return a.v; }
 
 // ---------------------------------------------------------------- the model, ONE source for T = float and T = Dual<N>
 // Every quantity is affine in (col, row) with coefficients that depend on the parameters only, so the per-block
@@ -203,17 +68,6 @@ struct CamModel {
     lat = -(datan2(yw, dsqrt(h2)) * kRad2Deg);
   }
 };
-
-// Huber by IRLS: weight of a residual of norm r, and rho(r)
-__device__ __forceinline__ void loss_of(float r, int huber, float delta, float* w, float* rho) {
-  if (huber && r > delta) {
-    *w = delta / r;
-    *rho = delta * (r - 0.5f * delta);
-  } else {
-    *w = 1.f;
-    *rho = 0.5f * r * r;
-  }
-}
 
 // per-block record (FIT_REC doubles): [0, NH) upper triangle of J^T W J row by row, [NH, NH + NP) J^T W r, then the cost,
 // sum |r_up|^2, sum r_lat^2 and the valid pixels
@@ -308,12 +162,6 @@ __device__ void write_out(float* o, const double* st) {
   o[PF_FIT_COL_ITERATIONS] = (float)fmax(st[S_NEV] - 1.0, 0.0);
   o[PF_FIT_COL_CONVERGED] = st[S_CONV] == 1.0 ? 1.f : 0.f;
   o[PF_FIT_COL_VALID_PIXELS] = (float)n;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 }  // namespace

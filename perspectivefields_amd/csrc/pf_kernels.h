@@ -394,6 +394,16 @@ int fit_blocks_per_image(int H, int W);
 void launch_fit_init(const FitBatch& fb, const FitParams& prm, hipStream_t s);
 void launch_fit_iteration(const FitBatch& fb, const FitParams& prm, hipStream_t s);  // one accumulate + solve pair
 
+// the same fit with the Unified Spherical Model's xi as one more parameter (fit_camera_usm.hip, include/pf_hip.h pf_fit_camera_usm).
+// It takes a FitBatch with its own strides: part [nblk][USMFIT_REC], state [n][USMFIT_STATE], out [n][PF_USMFIT_COLS], init [n][6];
+// FitParams::free_pp selects the 6-parameter fit (otherwise 4: roll, pitch, f, xi)
+constexpr int USMFIT_STATE = 48;  // doubles of per-image LM state
+constexpr int USMFIT_REC = 32;    // doubles of one accumulate block's partial record
+void launch_usmfit_init(const FitBatch& fb, const FitParams& prm, hipStream_t s);
+void launch_usmfit_iteration(const FitBatch& fb, const FitParams& prm, hipStream_t s);  // one accumulate + solve pair
+// camera parameters {roll, pitch (rad), focal_rel, cx_rel, cy_rel, xi} (device) -> up [2][H][W], latitude [H][W] degrees, NaN without a ray
+void launch_fields_usm(const float* cam6, int H, int W, float* up, float* lat, hipStream_t s);
+
 // equirectangular panorama -> camera views + ground-truth fields (pano_crop.hip, include/pf_hip.h pf_pano_crop): up to
 // PanoBatch::MAX crops of one output size per launch, per-crop panorama pointers and sizes in the kernel arguments
 struct PanoBatch {

@@ -469,8 +469,8 @@ class PerspectiveFields(nn.Module):
     def fit_camera(self, preds, **kw):
         """Camera parameters fitted to the dense fields of one inference() result (a dict) or of an inference_batch() list, on the
         GPU (see fit_camera_params for the options and the returned entries).  Works on every zoo version, PersNet included.
-        init="paramnet" starts from the result's own ParamNet scalars (ParamNet models only).  Returns new dicts; the
-        inference results are not changed."""
+        init="paramnet" starts from the result's own ParamNet scalars (ParamNet models only; at xi = 0 with distortion=True).  Returns
+        new dicts; the inference results are not changed."""
         single = isinstance(preds, dict)
         plist = [preds] if single else list(preds)
         if isinstance(kw.get("init"), str):
@@ -627,12 +627,17 @@ class PerspectiveFields(nn.Module):
     _DEVICE_FOCAL_ORDER = ("roll", "pitch", "general_vfov", "rel_cx", "rel_cy")   # every ParamNetConvNextRegress entry of the zoo (config/paramnet_*_rpfpp.yaml:32-37)
 
 
-def fields_from_params(roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, height=None, width=None, mode="deg", device=None):
+def fields_from_params(roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, height=None, width=None, mode="deg", device=None, xi=0.0):
     """Camera parameters -> (up field (2,H,W) unit vectors, latitude map (H,W) in degrees) on the GPU: the step the
     reference's demos run right after inference (utils/utils.py:325-381 -> PanoCam.get_up_general / get_lat_general,
     utils/panocam.py:451-556), e.g. to compare the ParamNet output with the predicted fields.  Same layout and units as
     `pred_gravity_original` / `pred_latitude_original`.  Arguments may be Python floats or 0-d tensors (the `pred_*`
-    entries of an inference dict: they stay on the device, no host round trip); angles in degrees unless mode="rad"."""
+    entries of an inference dict: they stay on the device, no host round trip); angles in degrees unless mode="rad".
+
+    xi: mirror parameter of the Unified Spherical Model (the `xi` of crop_panorama, `pred_xi` of fit_camera_params(distortion=True)).
+    The Python number 0 (the default) is the pinhole model above.  Anything else -- a non-zero number or a tensor, which stays on the
+    device and is not looked at on the host -- synthesises the USM fields of include/pf_hip.h pf_fields_from_params_usm: NaN where a
+    pixel has no ray (xi > 1), and for a tensor that holds 0 the same bits as the pinhole call."""
     import ctypes  # noqa: F401
 
     from .engine import _check, _stream_ptr, load_library
@@ -640,7 +645,8 @@ def fields_from_params(roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, height=No
     if height is None or width is None:
         raise ValueError("fields_from_params needs the output size (height, width)")
     dev = None
-    for v in (roll, pitch, rel_focal, rel_cx, rel_cy):
+    usm = torch.is_tensor(xi) or float(xi) != 0.0
+    for v in (roll, pitch, rel_focal, rel_cx, rel_cy, xi):
         if torch.is_tensor(v) and v.is_cuda:
             dev = v.device
     if dev is None:
@@ -649,7 +655,7 @@ def fields_from_params(roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, height=No
         raise PfError("fields_from_params runs on the GPU only (no CPU path)")
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    t = [torch.as_tensor(v, dtype=torch.float64).to(dev).reshape(()) for v in (roll, pitch, rel_focal, rel_cx, rel_cy)]
+    t = [torch.as_tensor(v, dtype=torch.float64).to(dev).reshape(()) for v in (roll, pitch, rel_focal, rel_cx, rel_cy) + ((xi,) if usm else ())]
     if mode == "deg":
         t[0], t[1] = torch.deg2rad(t[0]), torch.deg2rad(t[1])
     elif mode != "rad":
@@ -658,9 +664,9 @@ def fields_from_params(roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, height=No
     up = torch.empty((2, int(height), int(width)), dtype=torch.float32, device=dev)
     lat = torch.empty((int(height), int(width)), dtype=torch.float32, device=dev)
     lib = load_library()
+    entry = "pf_fields_from_params_usm" if usm else "pf_fields_from_params"
     with torch.cuda.device(dev):
-        _check(lib.pf_fields_from_params(dev.index, cam.data_ptr(), int(height), int(width), up.data_ptr(), lat.data_ptr(), _stream_ptr()),
-               None, "pf_fields_from_params")
+        _check(getattr(lib, entry)(dev.index, cam.data_ptr(), int(height), int(width), up.data_ptr(), lat.data_ptr(), _stream_ptr()), None, entry)
     return up, lat
 
 
@@ -684,9 +690,11 @@ def general_vfov_to_focal(rel_cx, rel_cy, gvfov_deg):
 _FIT_COLS = ("pred_roll", "pred_pitch", "pred_vfov", "pred_rel_focal", "pred_general_vfov", "pred_rel_cx", "pred_rel_cy",
              "fit_rms_up_deg", "fit_rms_lat_deg", "fit_cost", "fit_iterations", "fit_converged", "fit_valid_pixels")
 _FIT_LOSSES = {"l2": 0, "huber": 1}
+# columns of the pf_fit_camera_usm output row (PF_USMFIT_COL_*): the same, then xi
+_USMFIT_COLS = _FIT_COLS + ("pred_xi",)
 
 
-def fit_camera_params(up, lat, *, free_principal_point=False, loss="l2", huber_delta_deg=2.0, weights=(1.0, 1.0), max_iter=20, init=None):
+def fit_camera_params(up, lat, *, free_principal_point=False, loss="l2", huber_delta_deg=2.0, weights=(1.0, 1.0), max_iter=20, init=None, distortion=False):
     """Perspective fields -> camera parameters on the GPU: the inverse of `fields_from_params`, a per-image Levenberg-Marquardt
     least-squares fit of its model to an up field (2,H,W) and a latitude map (H,W) in degrees (the layout of
     `pred_gravity_original` / `pred_latitude_original`).  Model, loss and stopping rule: include/pf_hip.h pf_fit_camera.
@@ -700,7 +708,15 @@ def fit_camera_params(up, lat, *, free_principal_point=False, loss="l2", huber_d
     Returns one dict per image (a single dict for a single pair): pred_roll, pred_pitch, pred_vfov, pred_rel_focal,
     pred_general_vfov, pred_rel_cx, pred_rel_cy (angles in degrees), fit_rms_up_deg, fit_rms_lat_deg, fit_cost, fit_iterations,
     fit_converged, fit_valid_pixels -- 0-d device tensors (no host synchronisation), so `fields_from_params` can take the
-    pred_* entries directly.  GPU only: CPU tensors raise PfError."""
+    pred_* entries directly.  GPU only: CPU tensors raise PfError.
+
+    distortion=True fits the Unified Spherical Model of crop_panorama(..., xi=) instead (include/pf_hip.h pf_fit_camera_usm): the
+    mirror parameter xi is free too -- 4 parameters, 6 with free_principal_point -- clamped to [-0.5, 2], and each dict gains `pred_xi`.
+    `init` dicts may carry `pred_xi` (default 0); without `init` the start is the pinhole one at xi = 0, which recovers xi <= 1; for
+    xi > 1 (part of the image has no ray) give a start.  pred_vfov / pred_general_vfov keep their formulas in rel_focal, rel_cx and
+    rel_cy: under xi != 0 they describe the intrinsics, not the angle the image subtends.  fit_valid_pixels counts the pixels with finite
+    input and a ray.  `fields_from_params(..., xi=d["pred_xi"])` turns a result back into fields.  distortion=False is the pinhole fit,
+    unchanged."""
     from .engine import _check, _stream_ptr, load_library
 
     single = torch.is_tensor(up)
@@ -731,7 +747,8 @@ def fit_camera_params(up, lat, *, free_principal_point=False, loss="l2", huber_d
         for d in inits:
             z = torch.zeros((), dtype=torch.float64, device=dev)
             v = [torch.as_tensor(d[k], dtype=torch.float64).to(dev).reshape(()) for k in ("pred_roll", "pred_pitch", "pred_rel_focal")]
-            v += [torch.as_tensor(d[k], dtype=torch.float64).to(dev).reshape(()) if k in d else z for k in ("pred_rel_cx", "pred_rel_cy")]
+            v += [torch.as_tensor(d[k], dtype=torch.float64).to(dev).reshape(()) if k in d else z
+                  for k in ("pred_rel_cx", "pred_rel_cy") + (("pred_xi",) if distortion else ())]
             v[0], v[1] = torch.deg2rad(v[0]), torch.deg2rad(v[1])
             rows.append(torch.stack(v))
         d_init = torch.stack(rows).to(torch.float32).contiguous()
@@ -739,17 +756,18 @@ def fit_camera_params(up, lat, *, free_principal_point=False, loss="l2", huber_d
     p_up = (ctypes.c_void_p * B)(*[u.data_ptr() for u in ups])
     p_lat = (ctypes.c_void_p * B)(*[l.data_ptr() for l in lats])
     lib = load_library()
-    ws_n = int(lib.pf_fit_camera_workspace_bytes(B, hw))
+    entry, cols = ("pf_fit_camera_usm", _USMFIT_COLS) if distortion else ("pf_fit_camera", _FIT_COLS)
+    ws_n = int(getattr(lib, entry + "_workspace_bytes")(B, hw))
     if ws_n == 0:
         small = [tuple(u.shape[1:]) for u in ups if min(u.shape[1:]) < 8]
         raise PfError(f"fit_camera_params: images must be at least 8 x 8 (got {small})")
     ws = torch.empty(ws_n, dtype=torch.uint8, device=dev)
-    out = torch.empty((B, len(_FIT_COLS)), dtype=torch.float32, device=dev)
+    out = torch.empty((B, len(cols)), dtype=torch.float32, device=dev)
     w_up, w_lat = (float(w) for w in weights)
     with torch.cuda.device(dev):
-        _check(lib.pf_fit_camera(dev.index, B, hw, p_up, p_lat, d_init.data_ptr() if d_init is not None else None, int(bool(free_principal_point)),
-                                 _FIT_LOSSES[loss], float(huber_delta_deg), w_up, w_lat, int(max_iter), out.data_ptr(), ws.data_ptr(), ws_n,
-                                 _stream_ptr()), None, "pf_fit_camera")
+        _check(getattr(lib, entry)(dev.index, B, hw, p_up, p_lat, d_init.data_ptr() if d_init is not None else None, int(bool(free_principal_point)),
+                                   _FIT_LOSSES[loss], float(huber_delta_deg), w_up, w_lat, int(max_iter), out.data_ptr(), ws.data_ptr(), ws_n,
+                                   _stream_ptr()), None, entry)
     iters = out[:, 10].to(torch.int32)
     conv = out[:, 11] != 0
     valid = out[:, 12].to(torch.int64)
@@ -757,6 +775,8 @@ def fit_camera_params(up, lat, *, free_principal_point=False, loss="l2", huber_d
     for i in range(B):
         d = {k: out[i, j] for j, k in enumerate(_FIT_COLS[:10])}
         d["fit_iterations"], d["fit_converged"], d["fit_valid_pixels"] = iters[i], conv[i], valid[i]
+        if distortion:
+            d["pred_xi"] = out[i, 13]
         res.append(d)
     return res[0] if single else res
 
