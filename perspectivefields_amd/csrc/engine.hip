@@ -2115,8 +2115,8 @@ struct FitKind {
   void (*init)(const FitBatch&, const FitParams&, hipStream_t);
   void (*iteration)(const FitBatch&, const FitParams&, hipStream_t);
 };
-static const FitKind kFitPinhole{"pf_fit_camera", FIT_STATE, FIT_REC, 5, PF_FIT_COLS, launch_fit_init, launch_fit_iteration};
-static const FitKind kFitUsm{"pf_fit_camera_usm", USMFIT_STATE, USMFIT_REC, 6, PF_USMFIT_COLS, launch_usmfit_init, launch_usmfit_iteration};
+static const FitKind kFitPinhole{"pf_fit_camera", FIT_STATE, FIT_REC, 5, PF_FIT_COLS, launch_fit_init<PinholeFit>, launch_fit_iteration<PinholeFit>};
+static const FitKind kFitUsm{"pf_fit_camera_usm", USMFIT_STATE, USMFIT_REC, 6, PF_USMFIT_COLS, launch_fit_init<UsmFit>, launch_fit_iteration<UsmFit>};
 static size_t fit_state_bytes(const FitKind& fk, int B) { return ((size_t)B * fk.state * sizeof(double) + 255) & ~(size_t)255; }
 static size_t fit_part_bytes(const FitKind& fk, int H, int W) { return ((size_t)fit_blocks_per_image(H, W) * fk.rec * sizeof(double) + 255) & ~(size_t)255; }
 

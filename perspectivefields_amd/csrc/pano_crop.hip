@@ -28,7 +28,7 @@ namespace pf {
 
 namespace {
 
-constexpr float kInv2Pi = 0.15915494309189535f, kInvPi = 0.3183098861837907f, kRad2Deg = 57.29577951308232f;
+constexpr float kInv2Pi = 0.15915494309189535f, kInvPi = 0.3183098861837907f;
 
 struct CropConsts {
   float R[9];  // camera -> world, row major
@@ -36,23 +36,6 @@ struct CropConsts {
   float F, invF, Cx, Cy, xi, yaw_t, sx, sy;
   PinholeFields pin;  // the xi == 0 labels
 };
-
-__device__ __forceinline__ bool usm_ray(float x, float y, float xi, float* X) {
-  const float r2 = x * x + y * y;
-  const float disc = 1.f + (1.f - xi * xi) * r2;
-  if (!(disc >= 0.f)) return false;
-  const float eta = (xi + sqrtf(disc)) / (1.f + r2);
-  X[0] = eta * x;
-  X[1] = eta * y;
-  X[2] = eta - xi;
-  return true;
-}
-
-__device__ __forceinline__ void to_world(const CropConsts& c, const float* X, float* Xw) {
-  Xw[0] = c.R[0] * X[0] + c.R[1] * X[1] + c.R[2] * X[2];
-  Xw[1] = c.R[3] * X[0] + c.R[4] * X[1] + c.R[5] * X[2];
-  Xw[2] = c.R[6] * X[0] + c.R[7] * X[1] + c.R[8] * X[2];
-}
 
 __device__ __forceinline__ float texel(const uint8_t* p, size_t i) { return (float)p[i]; }
 __device__ __forceinline__ float texel(const float* p, size_t i) { return p[i]; }
@@ -127,20 +110,13 @@ __global__ __launch_bounds__(256) void pano_crop_kernel(PanoBatch pb) {
     float X[3];
     if (usm_ray(((float)col + 0.5f - cc.Cx) * cc.invF, ((float)row + 0.5f - cc.Cy) * cc.invF, xi, X)) {
       float Xw[3];
-      to_world(cc, X, Xw);
+      to_world(cc.R, X, Xw);
       float t = cc.yaw_t + atan2f(Xw[0], Xw[2]) * kInv2Pi;
       t -= floorf(t);
       const float u = t * (float)Wp - 0.5f;
       const float v = (0.5f + atan2f(Xw[1], sqrtf(Xw[0] * Xw[0] + Xw[2] * Xw[2])) * kInvPi) * (float)Hp - 0.5f;
       sample(pano, Hp, Wp, u, v, img[k]);
-      if (LABELS && xi != 0.f) {
-        const float D = X[2] + xi;
-        const float s = cc.g[2] + xi * (X[0] * cc.g[0] + X[1] * cc.g[1] + X[2] * cc.g[2]);
-        const float a = cc.g[0] * D - X[0] * s, b = cc.g[1] * D - X[1] * s;
-        const float inv = 1.f / sqrtf(a * a + b * b);
-        ux[k] = a * inv;
-        uy[k] = b * inv;
-      }
+      if (LABELS && xi != 0.f) usm_up_of_ray(X, cc.g, xi, &ux[k], &uy[k]);
     }
     if (LABELS) {
       if (xi == 0.f) {
@@ -149,9 +125,7 @@ __global__ __launch_bounds__(256) void pano_crop_kernel(PanoBatch pb) {
         uy[k] = o.uy;
         lat[k] = o.lat;
       } else if (usm_ray(((float)col * cc.sx - cc.Cx) / cc.F, ((float)row * cc.sy - cc.Cy) / cc.F, xi, X)) {
-        float Xw[3];
-        to_world(cc, X, Xw);
-        lat[k] = -atan2f(Xw[1], sqrtf(Xw[0] * Xw[0] + Xw[2] * Xw[2])) * kRad2Deg;
+        lat[k] = usm_lat_of_ray(X, cc.R);
       }
     }
   }

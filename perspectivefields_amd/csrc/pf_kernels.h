@@ -371,10 +371,15 @@ void launch_fields_from_params(const float* cam5, int H, int W, float* up, float
 // ParamNet scalar formulas (param_network.py:62-67): raw [B][nraw] -> [B][8] (layout: include/pf_hip.h)
 void launch_paramnet_scalars(const float* raw, int nraw, float* out8, int B, int mode, hipStream_t s);
 
-// perspective fields -> camera parameters (fit_camera.hip, include/pf_hip.h pf_fit_camera): up to FitBatch::MAX images per
-// launch, per-image sizes and pointers in the kernel arguments
-constexpr int FIT_STATE = 40;  // doubles of per-image LM state
-constexpr int FIT_REC = 24;    // doubles of one accumulate block's partial record
+// perspective fields -> camera parameters: one Levenberg-Marquardt driver (fit_lm.h) over two camera models, each a traits type Fit.
+//   PinholeFit (fit_camera.hip, include/pf_hip.h pf_fit_camera): theta [5] = roll, pitch, f, cx, cy; out [n][PF_FIT_COLS]
+//   UsmFit (fit_camera_usm.hip, pf_fit_camera_usm): theta [6], the Unified Spherical Model's xi as one more parameter; out [n][PF_USMFIT_COLS]
+// FitParams::free_pp selects the fit of all of theta (otherwise cx, cy are held: 3 / 4 parameters).  Up to FitBatch::MAX images per launch,
+// per-image sizes and pointers in the kernel arguments; the strides of part, state, out and init are the model's
+struct PinholeFit;
+struct UsmFit;
+constexpr int FIT_STATE = 40, USMFIT_STATE = 48;  // Fit::STATE: doubles of per-image LM state
+constexpr int FIT_REC = 24, USMFIT_REC = 32;      // Fit::REC: doubles of one accumulate block's partial record
 struct FitParams {
   int free_pp, loss;
   float huber_delta, w_up, w_lat;
@@ -385,22 +390,20 @@ struct FitBatch {
   int H[MAX], W[MAX], nblk[MAX];
   const float* up[MAX];   // [2][H][W]
   const float* lat[MAX];  // [H][W] degrees
-  double* part[MAX];      // [nblk][FIT_REC]
-  double* state;          // [n][FIT_STATE]
-  float* out;             // [n][PF_FIT_COLS]
-  const float* init;      // NULL or [n][5]
+  double* part[MAX];      // [nblk][Fit::REC]
+  double* state;          // [n][Fit::STATE]
+  float* out;             // [n][Fit::COLS]
+  const float* init;      // NULL or [n][Fit::NTH]
 };
-int fit_blocks_per_image(int H, int W);
+// accumulate blocks (= partial records) of an image: one per 4096 pixels, at most 256
+inline int fit_blocks_per_image(int H, int W) {
+  const long nb = ((long)H * W + 4095) / 4096;
+  return (int)(nb < 1 ? 1 : nb > 256 ? 256 : nb);
+}
+template <class Fit>
 void launch_fit_init(const FitBatch& fb, const FitParams& prm, hipStream_t s);
+template <class Fit>
 void launch_fit_iteration(const FitBatch& fb, const FitParams& prm, hipStream_t s);  // one accumulate + solve pair
-
-// the same fit with the Unified Spherical Model's xi as one more parameter (fit_camera_usm.hip, include/pf_hip.h pf_fit_camera_usm).
-// It takes a FitBatch with its own strides: part [nblk][USMFIT_REC], state [n][USMFIT_STATE], out [n][PF_USMFIT_COLS], init [n][6];
-// FitParams::free_pp selects the 6-parameter fit (otherwise 4: roll, pitch, f, xi)
-constexpr int USMFIT_STATE = 48;  // doubles of per-image LM state
-constexpr int USMFIT_REC = 32;    // doubles of one accumulate block's partial record
-void launch_usmfit_init(const FitBatch& fb, const FitParams& prm, hipStream_t s);
-void launch_usmfit_iteration(const FitBatch& fb, const FitParams& prm, hipStream_t s);  // one accumulate + solve pair
 // camera parameters {roll, pitch (rad), focal_rel, cx_rel, cy_rel, xi} (device) -> up [2][H][W], latitude [H][W] degrees, NaN without a ray
 void launch_fields_usm(const float* cam6, int H, int W, float* up, float* lat, hipStream_t s);
 

@@ -252,8 +252,9 @@ def test_new_kernels_are_in_the_library_without_scratch():
     kr = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(kr)
     by = {r["kernel"]: r for r in kr.kernels(lib)}
-    for k in ("pf::usmfit_init_kernel", "pf::usmfit_accum_kernel<4>", "pf::usmfit_accum_kernel<6>", "pf::usmfit_solve_kernel<4>", "pf::usmfit_solve_kernel<6>",
-              "pf::fields_usm_kernel", "pf::fit_accum_kernel<3>", "pf::fit_accum_kernel<5>"):
+    for k in ("pf::fit_init_kernel<pf::UsmFit>", "pf::fit_accum_kernel<pf::UsmFit, 4>", "pf::fit_accum_kernel<pf::UsmFit, 6>", "pf::fit_solve_kernel<pf::UsmFit, 4>",
+              "pf::fit_solve_kernel<pf::UsmFit, 6>", "pf::fields_usm_kernel", "pf::fit_accum_kernel<pf::PinholeFit, 3>", "pf::fit_accum_kernel<pf::PinholeFit, 5>",
+              "pf::fit_init_kernel<pf::PinholeFit>", "pf::fit_solve_kernel<pf::PinholeFit, 3>", "pf::fit_solve_kernel<pf::PinholeFit, 5>"):
         assert k in by, k
         assert by[k]["spill"] == 0 and by[k]["scratch"] == 0, by[k]
-    assert kr.blocks_per_cu(by["pf::usmfit_accum_kernel<6>"]) >= 3   # no worse than the 5-parameter pinhole kernel
+    assert kr.blocks_per_cu(by["pf::fit_accum_kernel<pf::UsmFit, 6>"]) >= 3   # no worse than the 5-parameter pinhole kernel
