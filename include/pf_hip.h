@@ -262,7 +262,8 @@ int pf_debug_ranges(pf_handle h, int max_records, char* names /*[max][96]*/, lon
 #define PF_DISPATCH_FORK_ALLOC_CONFLICTS 14   /* fork windows in which BOTH the copy and the parent allocated (two streams, one scratch offset): must be 0 */
 #define PF_DISPATCH_REAL_PEAK_BYTES 15        /* what the forward allocated from the workspace (main region + ParamNet region) */
 #define PF_DISPATCH_DRY_PEAK_BYTES 16         /* what pf_workspace_bytes' dry run sized for them; real > dry in either region: the call returns PF_ERR_WORKSPACE */
-#define PF_DISPATCH_COLS 17
+#define PF_DISPATCH_CNX_RB_LAUNCHES 17        /* row-block fused ConvNeXt block MLPs of the 384- / 768-channel stages (cnx_rb.hip); not part of RB_LAUNCHES */
+#define PF_DISPATCH_COLS 18
 int pf_last_dispatch(pf_handle h, int64_t* out, int n);
 
 /* The same for a whole batch in one launch per 32 images (the reference's per-image Python loop,
@@ -489,7 +490,8 @@ int pf_op_thin128(int device, const float* d_x, long rows, const float* h_weight
 int pf_op_rb_srkv(int device, const float* d_x, int B, int Hr, int Wr, int C, const float* h_ln1_gamma, const float* h_ln1_beta, float eps1, const float* h_sr_w,
                   const float* h_sr_b, const float* h_srn_gamma, const float* h_srn_beta, float eps2, const float* h_kv_w, const float* h_kv_b, float* d_kv, int iters,
                   float* ms_out, void* stream);
-/* One ConvNeXt block MLP in one kernel (cnx_mlp.hip): y += ls * pwconv2(GELU(pwconv1(LayerNorm(d)))), convnext.py:49-58; C = 96 or 192, weights
+/* One ConvNeXt block MLP in one kernel: y += ls * pwconv2(GELU(pwconv1(LayerNorm(d)))), convnext.py:49-58; C = 96 or 192 (cnx_mlp.hip: hidden map in
+ * registers) or C = 384 or 768 (cnx_rb.hip: row blocks resident in LDS); weights
  * in the reference's shapes (pwconv1 [4C][C], pwconv2 [C][4C], layer scale ls [C]); y is read (residual) and written.  iters > 0 additionally times
  * `iters` launches (avg ms in *ms_out; y is then garbage). */
 int pf_op_cnx_mlp(int device, const float* d_d, float* d_y, long rows, int C, const float* h_w1, const float* h_b1, const float* h_ln_gamma, const float* h_ln_beta,

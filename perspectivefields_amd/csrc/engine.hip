@@ -79,7 +79,8 @@ struct Head {
   ConvW lin[4], proc[4], fold[4], r1c1[4], r1c2[4], r2c1[4], r2c2[4], conv0, conv1, predcls;
   float* predw = nullptr; float* predb = nullptr; int nout = 0;
 };
-struct CnxBlock { float out_limit = 65504.f; /* window of the residual stream this block writes: the next block's depthwise conv */ DwW dw; LNW n; ConvW pw1, pw2; unsigned short* mlp_w = nullptr; float* mlp_tab = nullptr; /* fused MLP (cnx_mlp.hip), when built */ };
+struct CnxBlock { float out_limit = 65504.f; /* window of the residual stream this block writes: the next block's depthwise conv */ DwW dw; LNW n; ConvW pw1, pw2; unsigned short* mlp_w = nullptr; float* mlp_tab = nullptr; /* fused MLP (cnx_mlp.hip), when built */
+                  unsigned short* rb_w = nullptr; size_t rb_w_bytes = 0; float* rb_tab = nullptr; /* row-block fused MLP (cnx_rb.hip: C = 384 / 768), when built */ };
 struct Cnx { ConvW stem, ds[3]; LNW stemn, dsn[3], norm; std::vector<CnxBlock> blocks[4]; float* headw = nullptr; float* headb = nullptr; int nout = 0; };
 
 // Split-bf16 activation tensor (sb_split.h): three exact bf16 planes `plane` elements apart.
@@ -357,6 +358,13 @@ struct pf_engine {
                              // (mit_mlp.hip: hidden map in LDS / registers only); split-f16 scheme only
   bool fuse_cnx_mlp = true;  // PF_FUSE_CNX_MLP=0: ConvNeXt blocks of the 96- and 192-channel stages as LayerNorm-fused pwconv1 + pwconv2 GEMMs instead of
                              // the one-kernel MLP (cnx_mlp.hip, hidden map in registers only); split-f16 scheme only
+  int cnx_rb = 1;            // PF_CNX_RB: ConvNeXt blocks of the 384- / 768-channel stages as ONE row-block kernel (cnx_rb.hip: rows resident in LDS, hidden map never in HBM)
+                             // instead of LayerNorm-fused pwconv1 + pwconv2 on the generic tile.  Low two bits: 0 = GEMM pair, 1 = where the batch gives the stage at least
+                             // cnx_rb_min_blocks[stage] row blocks, 2 = whenever supported (tests); + 4 = stage 3 (C = 384) only.  Split-f16 scheme only, not with PF_SBA
+  int cnx_rb_min_blocks[2] = {96, 192};  // PF_CNX_RB_MIN_BLOCKS / PF_CNX_RB_MIN_BLOCKS_768: one block per CU and one block's latency per launch (90 / 210 us however few blocks
+                             // there are), so the GEMM pair wins below a batch.  Defaults 3/8 and 3/4 of the device's CU count: C = 384 (64-row blocks, 6.25 per image) from
+                             // B = 16, C = 768 (32-row blocks, 3.125 per image) from B = 62.  Alone, 50 blocks take 90 us against 69 us for the pair and a joined forward of
+                             // B = 8 is 0.42 ms slower with them, B = 12 0.17 ms; at 100 blocks it is 94 against 105 us and B = 16 is level (profiles/r07_cnx_rb.md)
   bool fold_mlp = true;      // PF_FOLD_MLP=0 keeps Linear(C->768) and conv3x3(768->256) as two kernels
   int nterms = NT_F16X3;     // pf_set_precision: NT_F16X3 = 2-way fp16 split, 3 MFMAs per product (default parity mode); 6 = exact 3-way bf16 split
                              // (fp32-accurate, PF_PRECISION_FP32_BF16X6); 3 = "bf16x3", 1 = "bf16" (reduced precision, not parity modes)
@@ -796,6 +804,17 @@ struct pf_engine {
             cb.mlp_w = upload_u16(wpk);
             cb.mlp_tab = upload(tab);
           }
+          // built whatever the precision mode or the batches to come (pf_set_precision may switch after the weights are loaded, the gate looks at each forward's batch):
+          // 4.7 MB per 384-channel block, 19 MB per 768-channel block, 100 MB of HBM in all beside the GEMM pair's weights; PF_CNX_RB=5 leaves the 57 MB of stage 4 out
+          if ((cnx_rb & 3) && cnx_rb_supported(C) && !((cnx_rb & 4) && C != 384)) {
+            std::vector<unsigned short> wpk;
+            std::vector<float> tab;
+            cnx_rb_pack(get(b + ".pwconv1.weight", {4 * C, C}).data.data(), get(b + ".pwconv1.bias", {4 * C}).data.data(), get(b + ".pwconv2.weight", {C, 4 * C}).data.data(),
+                        get(b + ".pwconv2.bias", {C}).data.data(), gm.data(), C, &wpk, &tab);
+            cb.rb_w = upload_u16(wpk);
+            cb.rb_w_bytes = wpk.size() * 2;
+            cb.rb_tab = upload(tab);
+          }
           cnx.blocks[s].push_back(cb);
         }
       }
@@ -812,7 +831,7 @@ struct pf_engine {
       for (int s = 0; s < 4; ++s)
         for (int j = 0; j < CNX_DEPTHS[s]; ++j) {
           const std::string b = p + "stages." + std::to_string(s) + "." + std::to_string(j);
-          if (cnx.blocks[s][j].mlp_w) note_static(mlp_hidden_bound(b + ".norm", b + ".pwconv1", "", CNX_DIMS[s]), 65504.f);  // hidden map of the fused block MLP (registers only)
+          if (cnx.blocks[s][j].mlp_w || cnx.blocks[s][j].rb_w) note_static(mlp_hidden_bound(b + ".norm", b + ".pwconv1", "", CNX_DIMS[s]), 65504.f);  // hidden map of the fused block MLP (registers only)
         }
       cnx.norm = make_ln(p + "norm", CNX_DIMS[3], 1e-6f);
       cnx.headw = upload(get(p + "head.weight", {cnx.nout, CNX_DIMS[3]}).data);
@@ -1417,6 +1436,9 @@ struct pf_engine {
       const Ten dn = S ? Ten(nullptr, c.alloc_sb(M * C)) : Ten(d);
       const Ten hb = c.ten(M * 4 * C, !S, S);
       int blk = -1;
+      // row-block form of the block MLP: one block per CU and one round, so it needs a batch that gives the stage enough row blocks
+      const long cnx_rb_blocks = cnx_rb_supported(C) ? (M + cnx_rb_rows(C) - 1) / cnx_rb_rows(C) : 0;
+      const bool use_cnx_rb = (cnx_rb & 3) && nterms == NT_F16X3 && !S && !c.tuning && cnx_rb_blocks > 0 && ((cnx_rb & 3) == 2 || cnx_rb_blocks >= cnx_rb_min_blocks[C == 384 ? 0 : 1]);
       for (CnxBlock& cb : cnx.blocks[s]) {
         if (blk >= 0) tap(c, fmt("pn.s%d.b%d", s + 1, blk), y, B, h, h, C);
         ++blk;
@@ -1429,6 +1451,18 @@ struct pf_engine {
           if (!c.dry) {
             ProfScope ps(c.prof, c.s, PC_IGEMM_SB, 2.0 * 2.0 * M * (double)C * 4 * C, (int)M, C, 8 * C, 1);
             launch_cnx_mlp(d, y, cb.mlp_w, cb.mlp_tab, M, C, cb.n.eps, c.s, d_sat, cb.out_limit);
+          }
+          continue;
+        }
+        if (cb.rb_w && use_cnx_rb) {                  // the same, rows resident in LDS (cnx_rb.hip)
+          range_in(c, fmt("cnx_rb s%d.b%d d (LN input)", s + 1, blk), d, (size_t)M * C);
+          if (!c.dry) {
+            CnxRbArgs a;
+            a.d = d; a.y = y; a.w = cb.rb_w; a.w_bytes = cb.rb_w_bytes; a.tab = cb.rb_tab; a.ln_g = cb.n.g; a.ln_b = cb.n.b; a.ln_eps = cb.n.eps; a.M = (int)M;
+            a.sat = d_sat; a.sat_limit = cb.out_limit;
+            ProfScope ps(c.prof, c.s, PC_IGEMM_SB, 2.0 * 2.0 * M * (double)C * 4 * C, (int)M, C, 8 * C, 1);
+            c.count(PF_DISPATCH_CNX_RB_LAUNCHES);
+            launch_cnx_rb(a, C, c.s);
           }
           continue;
         }
@@ -1644,6 +1678,10 @@ int pf_create(pf_handle* out, int device, int arch) {
     e->rb_min_blocks = e->num_cus * 3 / 4;  // "the last round of blocks nearly fills the chip": 192 of 256 CUs
   }
   if (const char* v = getenv("PF_RB_MIN_BLOCKS")) e->rb_min_blocks = atoi(v);
+  if (const char* v = getenv("PF_CNX_RB")) e->cnx_rb = atoi(v);
+  if (!host_only) { e->cnx_rb_min_blocks[0] = e->num_cus * 3 / 8; e->cnx_rb_min_blocks[1] = e->num_cus * 3 / 4; }
+  if (const char* v = getenv("PF_CNX_RB_MIN_BLOCKS")) e->cnx_rb_min_blocks[0] = atoi(v);
+  if (const char* v = getenv("PF_CNX_RB_MIN_BLOCKS_768")) e->cnx_rb_min_blocks[1] = atoi(v);
 #ifdef PF_TUNING_BUILD
 #endif
   if (const char* v = getenv("PF_SIDE_STREAM")) e->side_stream_mode = atoi(v);
@@ -1661,6 +1699,7 @@ int pf_create(pf_handle* out, int device, int arch) {
   if (!e->split_bf16 || e->sba) e->fuse_ln = false;  // the fused form lives in the split GEMM kernels and reads fp32 rows
   if (!e->split_bf16 || e->sba) e->fuse_cnx_mlp = false;
   if (!e->split_bf16 || e->sba) e->fuse_mit_mlp = false;
+  if (!e->split_bf16 || e->sba) e->cnx_rb = 0;
 
   tune_cache_load(e);
   *out = e;

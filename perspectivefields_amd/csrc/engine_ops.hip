@@ -373,20 +373,29 @@ int pf_op_cnx_mlp(int device, const float* d, float* y, long rows, int C, const 
   std::string err;
   int rc = check_device(device, &err);
   if (rc != PF_OK) { g_create_error = err; return rc; }
-  if (!cnx_mlp_supported(C) || !d || !y || rows <= 0) { g_create_error = "pf_op_cnx_mlp: C must be 96 or 192"; return PF_ERR_ARG; }
+  if ((!cnx_mlp_supported(C) && !cnx_rb_supported(C)) || !d || !y || rows <= 0 || rows > 0x7fffffffL / (4 * C)) { g_create_error = "pf_op_cnx_mlp: C must be 96, 192, 384 or 768"; return PF_ERR_ARG; }
   hipStream_t s = static_cast<hipStream_t>(stream);
   TmpDev tmp;
   std::vector<unsigned short> wpk;
   std::vector<float> tab;
-  cnx_mlp_pack(w1, b1, lng, lnb, w2, b2, ls, C, &wpk, &tab);
+  const bool rb = cnx_rb_supported(C);  // C = 384 / 768: the row-block form (cnx_rb.hip)
+  if (rb) cnx_rb_pack(w1, b1, w2, b2, ls, C, &wpk, &tab);
+  else cnx_mlp_pack(w1, b1, lng, lnb, w2, b2, ls, C, &wpk, &tab);
   const unsigned short* dw = tmp.up_u16(wpk);
   const float* dt = tmp.up(tab);
-  launch_cnx_mlp(d, y, dw, dt, rows, C, eps, s);
+  CnxRbArgs ra{};
+  if (rb) {
+    ra.d = d; ra.y = y; ra.w = dw; ra.w_bytes = wpk.size() * 2; ra.tab = dt; ra.ln_g = tmp.up(lng, C); ra.ln_b = tmp.up(lnb, C); ra.ln_eps = eps; ra.M = (int)rows;
+    ra.sat = nullptr; ra.sat_limit = 65504.f;
+    if (!dw || !dt || !ra.ln_g || !ra.ln_b) { g_create_error = "pf_op_cnx_mlp: hipMalloc failed"; tmp.sync_free(s); return PF_ERR_DEVICE; }
+  }
+  auto launch = [&]() { if (rb) launch_cnx_rb(ra, C, s); else launch_cnx_mlp(d, y, dw, dt, rows, C, eps, s); };
+  launch();
   if (iters > 0 && ms_out) {  // timing loop (y keeps accumulating: values are meaningless afterwards)
     hipEvent_t a, b;
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
     (void)hipEventRecord(a, s);
-    for (int i = 0; i < iters; ++i) launch_cnx_mlp(d, y, dw, dt, rows, C, eps, s);
+    for (int i = 0; i < iters; ++i) launch();
     (void)hipEventRecord(b, s);
     (void)hipEventSynchronize(b);
     float t = 0.f;

@@ -187,6 +187,44 @@ inline void rb_pack_w(const float* w, int N, int K, int cols, std::vector<unsign
   *inv = pl.inv_scale;
 }
 
+// Weight stream and tables of the row-block fused ConvNeXt block MLP (cnx_rb.hip), in execution order: per hidden chunk t of 128 columns
+//   W1 pass:    [k16 step < C/16][column tile < 4][plane][lane][8],    value = W1s[128 t + 32 ct + (lane & 31)][16 step + 8 (lane >> 5) + e]
+//   W2 K-slice: [k16 step < 8][column tile < C/32][plane][lane][8],    value = W2s[32 ct + (lane & 31)][128 t + 16 step + 8 (lane >> 5) + e]
+// (rb_pack_w's fragment order), W2'[n][j] = ls[n] W2[n][j] and b2' = ls b2 folded in fp64, per-output-channel power-of-two scales of the split-f16 scheme.  The
+// LayerNorm is NOT folded (the kernel normalises the rows while it stages them).  Zero padding of one W1 pass + RB_D W2 steps at the end: both rings read ahead.
+// tab: inv1[H], b1[H], inv2[C], b2'[C]
+inline void cnx_rb_pack(const float* w1, const float* b1, const float* w2, const float* b2, const float* ls, int C, std::vector<unsigned short>* stream, std::vector<float>* tab) {
+  const int H = 4 * C, HC = 128, NCH = H / HC, KC = C / 16, KC2 = HC / 16, NCT2 = C / 32;
+  std::vector<float> w1v(w1, w1 + (size_t)H * C), w2f((size_t)C * H), b2f(C);
+  for (int n = 0; n < C; ++n) {
+    for (int j = 0; j < H; ++j) w2f[(size_t)n * H + j] = (float)((double)w2[(size_t)n * H + j] * (double)ls[n]);
+    b2f[n] = (float)((double)b2[n] * (double)ls[n]);
+  }
+  const F16Planes p1 = split_f16x2(w1v, H), p2 = split_f16x2(w2f, C);
+  const size_t n1 = w1v.size(), n2 = w2f.size();
+  const size_t step1 = (size_t)4 * 2 * 512, step2 = (size_t)NCT2 * 2 * 512, chunk = KC * step1 + KC2 * step2;
+  stream->assign((size_t)NCH * chunk + KC * step1 + 4 * step2, 0);
+  for (int t = 0; t < NCH; ++t) {
+    unsigned short* o = stream->data() + (size_t)t * chunk;
+    for (int st = 0; st < KC; ++st)
+      for (int ct = 0; ct < 4; ++ct)
+        for (int p = 0; p < 2; ++p)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int e = 0; e < 8; ++e)
+              o[st * step1 + ((size_t)(ct * 2 + p) * 64 + lane) * 8 + e] = p1.planes[p * n1 + (size_t)(HC * t + 32 * ct + (lane & 31)) * C + 16 * st + 8 * (lane >> 5) + e];
+    o += KC * step1;
+    for (int st = 0; st < KC2; ++st)
+      for (int ct = 0; ct < NCT2; ++ct)
+        for (int p = 0; p < 2; ++p)
+          for (int lane = 0; lane < 64; ++lane)
+            for (int e = 0; e < 8; ++e)
+              o[st * step2 + ((size_t)(ct * 2 + p) * 64 + lane) * 8 + e] = p2.planes[p * n2 + (size_t)(32 * ct + (lane & 31)) * H + HC * t + 16 * st + 8 * (lane >> 5) + e];
+  }
+  tab->resize((size_t)2 * H + 2 * C);
+  for (int j = 0; j < H; ++j) { (*tab)[j] = p1.inv_scale[j]; (*tab)[H + j] = b1[j]; }
+  for (int n = 0; n < C; ++n) { (*tab)[2 * H + n] = p2.inv_scale[n]; (*tab)[2 * H + C + n] = b2f[n]; }
+}
+
 // Weights of the fused MiT block Mlp (mit_mlp.hip), one chunk of mit_mlp_chunk_bytes(C) per 32 hidden units t (layout: the kernel's header):
 // LayerNorm (norm2) folded into fc1 as fold_ln_linear, split-f16 planes in MFMA fragment order, depthwise taps [ky * 3 + kx][hidden] + bias.
 inline void mit_mlp_pack(const float* w1, const float* b1, const float* g, const float* be, const float* wdw /*[H][1][3][3]*/, const float* bdw, const float* w2, const float* b2,

@@ -304,6 +304,24 @@ void launch_nearest_nhwc4(const float* x, float* y, int B, int H, int W, int Ho,
 bool cnx_mlp_supported(int C);
 bool cnx_mlp_preferred(int C);  // the stages where the engine uses it
 void launch_cnx_mlp(const float* d, float* y, const unsigned short* wpk, const float* tab, long M, int C, float eps, hipStream_t s, unsigned* sat = nullptr, float sat_limit = 65504.f);
+// Row-block fused ConvNeXt block MLP (cnx_rb.hip, rb_common.h): the same block for C = 384 / 768 on blocks of 64 / 32 rows, hidden map in LDS only; d and y are
+// different buffers.  w / tab: packed by cnx_rb_pack (host_pack.h); LayerNorm gamma / beta are applied while the rows are staged
+struct CnxRbArgs {
+  const float* d;            // [M][C] depthwise conv output
+  float* y;                  // [M][C] residual stream, in and out
+  const unsigned short* w;   // weight stream: [hidden chunk of 128: W1 pass, W2 K-slice] ...
+  size_t w_bytes;
+  const float* tab;          // inv1 [4C], b1 [4C], inv2 [C], b2 [C] (layer scale folded)
+  const float* ln_g;
+  const float* ln_b;
+  float ln_eps;
+  int M;
+  unsigned* sat = nullptr;   // saturation watch of the residual stream (ConvParams::sat)
+  float sat_limit = 65504.f;
+};
+bool cnx_rb_supported(int C);
+int cnx_rb_rows(int C);      // rows per block
+void launch_cnx_rb(const CnxRbArgs& a, int C, hipStream_t s);
 // Fused MiT block Mlp (mit_mlp.hip): y = x + fc2(GELU(dwconv3x3(fc1(LayerNorm(x))))) for C = 64 / 128; x and y are different buffers.
 // wpk / tab2: packed by mit_mlp_pack (engine.hip), one chunk of mit_mlp_chunk_bytes(C) per 32 hidden units
 bool mit_mlp_supported(int C);

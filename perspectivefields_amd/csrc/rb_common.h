@@ -50,12 +50,13 @@ struct RbGeo {
 // of an XCD covering disjoint slices -- made the layers SLOWER in the pipeline: fc1 49 -> 63 us, proj 20 -> 30 us.  The warm-up loads are younger than the ring's
 // first steps, so the first counted vmcnt wait of the K loop also waits for every one of them, i.e. for HBM.)
 // Per-wave state of the weight stream: one VGPR offset (lane * 16 + running step offset), NW wave-uniform tile offsets
-template <class G>
+// D: ring depth in k16 steps (RB_D; a pass with few MFMAs per step -- cnx_rb.hip's GEMM 1, 6 per step -- needs more steps in flight to cover the same latency)
+template <class G, int D = RB_D>
 struct RbW {
   __amdgpu_buffer_rsrc_t rw;
   unsigned voff;          // lane * 16 + bytes of the steps already issued
   unsigned toff[G::NW];   // byte offset of this wave's column tiles inside a step (wave-uniform)
-  u32x4 f[RB_D][G::NW][2];
+  u32x4 f[D][G::NW][2];
   __device__ __forceinline__ void init(const unsigned short* w, size_t bytes, int wave, int lane) {
     rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(w), 0, (int)(bytes < 0x7fffffffUL ? bytes : 0x7fffffffUL), 0x00020000);
     voff = (unsigned)lane * 16u;
@@ -74,7 +75,7 @@ struct RbW {
   }
   __device__ __forceinline__ void prologue() {
 #pragma unroll
-    for (int d = 0; d < RB_D; ++d) load(d);
+    for (int d = 0; d < D; ++d) load(d);
   }
 };
 
@@ -145,8 +146,8 @@ __device__ __forceinline__ void rb_step_abl(f32x16 (&acc)[G::NACC], RbW<G>& W, i
   }
   W.advance();
 }
-template <class G, int ABL = 0>
-__device__ __forceinline__ void rb_step(f32x16 (&acc)[G::NACC], RbW<G>& W, int d, const RbA<G>& A, RbA<G>& An, const unsigned char* next_chunk, int lane, int xr) {
+template <class G, int ABL = 0, int D = RB_D>
+__device__ __forceinline__ void rb_step(f32x16 (&acc)[G::NACC], RbW<G, D>& W, int d, const RbA<G>& A, RbA<G>& An, const unsigned char* next_chunk, int lane, int xr) {
   if constexpr (ABL != 0) { rb_step_abl<G, ABL>(acc, W, d, A, An, next_chunk, lane, xr); return; }
   constexpr int X = G::CTW, XA = G::RT * G::CTW, RT = G::RT;  // the extra tile's fragment pair / accumulator
   An.read(next_chunk, lane, xr);

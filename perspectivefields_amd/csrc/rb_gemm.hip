@@ -123,6 +123,7 @@ __global__ __launch_bounds__(256, 1) void rb_linear_kernel(const RbLinArgs p) {
     W.prologue();
     RB_STAMP(1);
     if constexpr (LN) {  // two passes over the registers, like F.layer_norm: mean, then the variance of the centred row
+      // (cnx_rb.hip's LayerNorm is NOT this one bit for bit: it re-centres the row by the mean of the centred row, a third pass, which its constant-row test needs)
       float s = 0.f;
 #pragma unroll
       for (int i = 0; i < CPT; ++i)

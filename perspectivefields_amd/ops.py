@@ -243,7 +243,8 @@ def mit_mlp(x, fc1_w, fc1_b, ln_gamma, ln_beta, eps, dw_w, dw_b, fc2_w, fc2_b, i
 
 def cnx_mlp(d, y, w1, b1, ln_gamma, ln_beta, eps, w2, b2, layer_scale, iters=0):
     """One ConvNeXt block MLP in one kernel: returns y + layer_scale * pwconv2(GELU(pwconv1(LayerNorm(d)))) (y is not modified: a copy is
-    updated).  d, y: (rows, C) on the GPU, C = 96 or 192.  iters > 0: returns (result of the first launch is lost) the average ms per launch."""
+    updated).  d, y: (rows, C) on the GPU, C = 96 or 192 (cnx_mlp.hip), 384 or 768
+    (the row-block form, cnx_rb.hip).  iters > 0: returns (result of the first launch is lost) the average ms per launch."""
     lib = load_library()
     d = d.contiguous()
     out = y.contiguous().clone()
