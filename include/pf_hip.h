@@ -446,6 +446,10 @@ int pf_field_errors(int device, int batch, const int32_t* h_hw, const float* con
  * format: 0 = three bf16 planes (x == h + m + l exactly; read by the bf16 schemes), 1 = two fp16 planes of the split-f16
  * scheme (x ~ hi + lo, lo = fp16(x - hi) unscaled: what that scheme's GEMM computes from fp32 while staging; 4 bytes per element).
  * Producers write them for tensors that only feed GEMMs (PF_SBA=1); every *_planes argument is optional (NULL). */
+/* kernel-level entry points only: until called again, every pf_op_* launch of this thread hands `d_counter_u32` (NULL = off, the default) to its kernel as
+ * ConvParams::sat and friends, with `limit` as sat_limit.  Windows a kernel hard-codes (attention q 8188 in attn_block.hip, kv 4094 in rb_chain.hip) stay.
+ * The timing loops (iters > 0) and the *_bench entries run with the watch off. */
+int pf_op_set_saturation_watch(void* d_counter_u32, float limit);
 int pf_op_conv2d(int device, const float* d_x, const float* d_x2, int B, int H, int W, int C1, int C2,
                  const float* h_weight /*[Cout][C1+C2][KH][KW]*/, const float* h_bias /*[Cout] or NULL*/,
                  int Cout, int KH, int KW, int stride, int pad, int act /*0 none 1 relu 2 gelu*/,

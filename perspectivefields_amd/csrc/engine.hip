@@ -1207,7 +1207,7 @@ struct pf_engine {
             RbProjFc1Args a;
             a.attn = ab.f; a.x = x; a.w = mb.rpf.w; a.w_bytes = mb.rpf.bytes; a.proj_inv = mb.rproj.inv; a.proj_bias = mb.rproj.b;
             a.ln2_g = mb.n2.g; a.ln2_b = mb.n2.b; a.ln2_eps = mb.n2.eps; a.fc1_inv = mb.rfc1.inv; a.fc1_bias = mb.rfc1.b; a.hidden = hb;
-            a.B = B; a.tokens = (int)N; a.bpi = ((int)N + 63) / 64; a.sat = d_sat;
+            a.B = B; a.tokens = (int)N; a.bpi = ((int)N + 63) / 64; a.sat = d_sat; a.sat_limit = mb.rproj.sat_limit; a.hidden_limit = mb.rfc1.sat_limit;
             ProfScope ps(c.prof, c.s, PC_IGEMM_SB, 2.0 * M * (double)C * 5 * C, (int)M, 5 * C, C, 1);
             c.count(PF_DISPATCH_RB_LAUNCHES);
             launch_rb_proj_fc1(a, C, c.s);

@@ -5,7 +5,18 @@
 using namespace pf;
 using namespace pf_host;
 
+// pf_op_set_saturation_watch: the counter / limit every pf_op_* launch of this thread hands to its kernel (nullptr = off); the timing loops and *_bench entries run without
+static thread_local unsigned* t_op_sat = nullptr;
+static thread_local float t_op_sat_limit = 65504.f;
+
 extern "C" {
+
+int pf_op_set_saturation_watch(void* d_counter_u32, float limit) {
+  if (d_counter_u32 && !(limit > 0.f)) { g_create_error = "pf_op_set_saturation_watch: limit must be positive"; return PF_ERR_ARG; }
+  t_op_sat = static_cast<unsigned*>(d_counter_u32);
+  t_op_sat_limit = d_counter_u32 ? limit : 65504.f;
+  return PF_OK;
+}
 
 int pf_op_num_conv_tiles(void) { return conv_num_tiles(); }
 const char* pf_op_conv_tile_name(int id) { return conv_tile_name(id); }
@@ -50,6 +61,7 @@ int pf_op_conv2d(int device, const float* x, const float* x2, int B, int H, int 
   // split-plane INPUT: the plane format (bit 0 of x_plane_elems, sb_split.h) fixes the scheme: fp16 planes <-> split-f16, bf16 planes <-> bf16 schemes
   if (x_planes) p.nterms = (x_plane_elems & 1) ? NT_F16X3 : (p.nterms == NT_F16X3 ? 6 : p.nterms);
   p.wino_half = conv_wino_half_env();
+  p.sat = t_op_sat; p.sat_limit = t_op_sat_limit;
   p.finish();
   if ((!x && !x_planes) || (!y && !y_planes) || (C2 > 0 && !x2 && !x2_planes)) { g_create_error = "pf_op_conv2d: missing input or output"; return PF_ERR_ARG; }
   // an explicit tile that cannot read / write split planes is an error; with fp32 operands an unusable tile id falls back to the cost model
@@ -90,6 +102,7 @@ int pf_op_linear_ln(int device, const float* x, long rows, int K, const float* h
   p.Cout = N; p.act = act; p.post_relu = 0; p.nchw_out = 0;
   p.nterms = precision == PF_PRECISION_FP32_BF16X6 ? 6 : NT_F16X3;
   p.ln = 1; p.ln_eps = eps;
+  p.sat = t_op_sat; p.sat_limit = t_op_sat_limit;
   p.finish();
   if (tile_id >= 0 && !conv_tile_usable(p, tile_id)) { g_create_error = "pf_op_linear_ln: tile config cannot run the fused LayerNorm form"; return PF_ERR_ARG; }
   launch_conv_tile(p, tile_id, s);
@@ -116,7 +129,9 @@ int pf_op_rb_linear(int device, const float* x, long rows, int tokens, int K, co
   a.x = x; a.ln_g = hgamma ? tmp.up(std::vector<float>(hgamma, hgamma + K)) : nullptr; a.ln_b = hgamma ? tmp.up(std::vector<float>(hbeta, hbeta + K)) : nullptr; a.ln_eps = eps;
   a.w = tmp.up_u16(st); a.w_bytes = st.size() * 2; a.inv = tmp.up(inv); a.bias = tmp.up(std::vector<float>(hb, hb + N)); a.res = res; a.y = y;
   a.M = (int)rows; a.tokens = tokens; a.bpi = (tokens + 63) / 64; a.N = N; a.act = act;
+  a.sat = t_op_sat; a.sat_limit = t_op_sat_limit;
   launch_rb_linear(a, K, s);
+  a.sat = nullptr;  // the stamp and timing launches below run unwatched
   if (getenv("PF_RB_STAMPS") && !hgamma) {  // timing aid: the s_memtime stamps of block 17's four waves of one more launch, to stderr
     unsigned long long* ds = nullptr;
     if (hipMalloc(&ds, 4 * 64 * 8) == hipSuccess) {
@@ -172,7 +187,9 @@ int pf_op_rb_proj_fc1(int device, const float* attn, float* x, int B, int tokens
   a.attn = attn; a.x = x; a.w = tmp.up_u16(st1); a.w_bytes = st1.size() * 2; a.proj_inv = tmp.up(inv1); a.proj_bias = tmp.up(proj_b, C);
   a.ln2_g = tmp.up(ln2_g, C); a.ln2_b = tmp.up(ln2_b, C); a.ln2_eps = eps; a.fc1_inv = tmp.up(inv2); a.fc1_bias = tmp.up(fc1_b, 4 * C); a.hidden = hidden;
   a.B = B; a.tokens = tokens; a.bpi = (tokens + 63) / 64;
+  a.sat = t_op_sat; a.sat_limit = a.hidden_limit = t_op_sat_limit;
   launch_rb_proj_fc1(a, C, s);
+  a.sat = nullptr;
   if (iters > 0 && ms_out) {  // timing loop (x keeps accumulating: values are meaningless afterwards)
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -206,9 +223,11 @@ int pf_op_mit_attn64(int device, const float* x, const float* kv, float* y, int 
   attn64_pack(ln_g, ln_b, q_w, q_b, p_w, p_b, &wfr, &tab);
   MitAttn64Args a;
   a.x = x; a.kv = kv; a.y = y; a.wfr = tmp.up_u16(wfr); a.tab = tmp.up(tab); a.B = B; a.N = N; a.M = M; a.ln_eps = eps;
+  a.sat = t_op_sat; a.sat_limit = t_op_sat_limit;
   int cus = 256;
   { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount; }
   launch_mit_attn64(a, cus, s);
+  a.sat = nullptr;
   if (iters > 0 && ms_out) {  // timing loop (with y aliasing x the rows keep accumulating: values are meaningless afterwards)
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -243,9 +262,11 @@ int pf_op_stem7x7(int device, const float* x, float* y, int B, int H, int W, int
   Stem7Args a;
   a.x = x; a.y = y; a.wfr = tmp.up_u16(wfr); a.tab = tmp.up(tab); a.B = B; a.H = H; a.W = W; a.stride = stride;
   a.Ho = (H + 6 - 7) / stride + 1; a.Wo = (W + 6 - 7) / stride + 1; a.relu = relu; a.ln = ln_g ? 1 : 0; a.ln_eps = eps;
+  a.sat = t_op_sat; a.sat_limit = t_op_sat_limit;
   int cus = 256;
   { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount; }
   launch_stem7x7(a, cus, s);
+  a.sat = nullptr;
   if (iters > 0 && ms_out) {
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -275,9 +296,11 @@ int pf_op_thin128(int device, const float* x, long rows, const float* w, const f
   thin128_pack(w, bias, &wfr, &tab);
   ThinLinArgs a;
   a.x = x; a.res = res; a.y = y; a.wfr = tmp.up_u16(wfr); a.tab = tmp.up(tab); a.M = rows;
+  a.sat = t_op_sat; a.sat_limit = t_op_sat_limit;
   int cus = 256;
   { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount; }
   launch_thin128(a, cus, s);
+  a.sat = nullptr;
   if (iters > 0 && ms_out) {
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -319,7 +342,9 @@ int pf_op_rb_srkv(int device, const float* x, int B, int Hr, int Wr, int C, cons
   a.w = tmp.up_u16(st1); a.w_bytes = st1.size() * 2; a.sr_inv = tmp.up(inv1); a.sr_bias = tmp.up(sr_b, C);
   a.srn_g = tmp.up(srn_g, C); a.srn_b = tmp.up(srn_b, C); a.srn_eps = eps2; a.kv_inv = tmp.up(inv2); a.kv_bias = tmp.up(kv_b, 2 * C);
   a.kv = kv; a.B = B; a.Hr = Hr; a.Wr = Wr; a.bpi = (Hr * Wr + 31) / 32;
+  a.sat = t_op_sat;  // against the kernel's own window (4094)
   launch_rb_srkv(a, C, s);
+  a.sat = nullptr;
   if (iters > 0 && ms_out) {
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -350,7 +375,7 @@ int pf_op_mit_mlp(int device, const float* x, float* y, int B, int Hs, int Ws, i
   mit_mlp_pack(w1, b1, lng, lnb, wdw, bdw, w2, b2, C, &wpk, &tab2);
   const unsigned short* dw = tmp.up_u16(wpk);
   const float* dt = tmp.up(tab2);
-  launch_mit_mlp(x, y, dw, dt, B, Hs, Ws, C, eps, s);
+  launch_mit_mlp(x, y, dw, dt, B, Hs, Ws, C, eps, s, t_op_sat, t_op_sat_limit);
   if (iters > 0 && ms_out) {
     hipEvent_t a, b;
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);
@@ -386,11 +411,13 @@ int pf_op_cnx_mlp(int device, const float* d, float* y, long rows, int C, const 
   CnxRbArgs ra{};
   if (rb) {
     ra.d = d; ra.y = y; ra.w = dw; ra.w_bytes = wpk.size() * 2; ra.tab = dt; ra.ln_g = tmp.up(lng, C); ra.ln_b = tmp.up(lnb, C); ra.ln_eps = eps; ra.M = (int)rows;
-    ra.sat = nullptr; ra.sat_limit = 65504.f;
+    ra.sat = t_op_sat; ra.sat_limit = t_op_sat_limit;
     if (!dw || !dt || !ra.ln_g || !ra.ln_b) { g_create_error = "pf_op_cnx_mlp: hipMalloc failed"; tmp.sync_free(s); return PF_ERR_DEVICE; }
   }
-  auto launch = [&]() { if (rb) launch_cnx_rb(ra, C, s); else launch_cnx_mlp(d, y, dw, dt, rows, C, eps, s); };
+  unsigned* sat = t_op_sat;
+  auto launch = [&]() { if (rb) launch_cnx_rb(ra, C, s); else launch_cnx_mlp(d, y, dw, dt, rows, C, eps, s, sat, t_op_sat_limit); };
   launch();
+  sat = ra.sat = nullptr;
   if (iters > 0 && ms_out) {  // timing loop (y keeps accumulating: values are meaningless afterwards)
     hipEvent_t a, b;
     (void)hipEventCreate(&a); (void)hipEventCreate(&b);

@@ -139,9 +139,11 @@ int conv_splitk_factor(const ConvParams& p) {
   return conv_splitk_shape(p.M, p.Cout, p.KH, p.KWCp, p.groups, conv_splitk_env());
 }
 
-// y = post(act(oscale * sum_s partial[s] + bias) + res1), 4 outputs per thread
+// y = post(act(oscale * sum_s partial[s] + bias) + res1), 4 outputs per thread.  This kernel writes the layer's finished output, so the saturation watch of a split-K
+// layer (ConvParams::sat) lives here: the partial passes are not watched
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float4* __restrict__ partial, int S, long mn4, int n4, const float4* __restrict__ oscale,
-                                                            const float4* __restrict__ bias, int act, const float4* __restrict__ res1, int post_relu, float4* __restrict__ y) {
+                                                            const float4* __restrict__ bias, int act, const float4* __restrict__ res1, int post_relu, float4* __restrict__ y,
+                                                            unsigned* sat, float sat_limit) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < mn4; i += (long)gridDim.x * 256) {
     float4 v = partial[i];
     for (int k = 1; k < S; ++k) { const float4 q = partial[(long)k * mn4 + i]; v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
@@ -152,6 +154,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float4* __rest
     else if (act == ACT_GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
     if (res1) { const float4 q = res1[i]; v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w; }
     if (post_relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (sat) sat_watch4(sat, sat_limit, v.x, v.y, v.z, v.w);
     y[i] = v;
   }
 }
@@ -169,7 +172,7 @@ void launch_conv_sb(const ConvParams& p0, int sb_tile, hipStream_t s) {
       const ConvPtrs& q = p.g[g];
       hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(q.partial), p.splitk, mn4, p.Cout / 4,
                          reinterpret_cast<const float4*>(p.nterms == NT_F16X3 ? q.w_h16_inv_scale : nullptr), reinterpret_cast<const float4*>(q.bias), p.act,
-                         reinterpret_cast<const float4*>(q.res1), p.post_relu, reinterpret_cast<float4*>(q.y));
+                         reinterpret_cast<const float4*>(q.res1), p.post_relu, reinterpret_cast<float4*>(q.y), p.sat, p.sat_limit);
     }
   } } reduce_after{p, s};
   if (sb_tile >= conv_sb_num_tiles() - 2) {

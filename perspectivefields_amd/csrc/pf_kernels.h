@@ -113,9 +113,10 @@ struct ConvParams {
   unsigned x_bytes, x2_bytes, w_bytes;  // buffer sizes for the hardware range check (< 2 GiB each)
   unsigned w_sb_plane_bytes;            // bytes of one bf16 weight plane
   size_t x_sb_plane = 0, x2_sb_plane = 0, y_sb_plane = 0;  // elements between consecutive planes of x_sb / x2_sb / y_sb
-  // Always-on saturation watch (engine only; nullptr in the op entry points): every producer of a tensor that a split-f16 contraction will read counts the 16-byte
-  // groups of its output with an element beyond sat_limit (or NaN) into *sat -- one compare per group and, in a healthy network, no atomic ever.  The limit is the
-  // CONSUMER's window: 65504, 65504 / 4 in front of a Winograd conv (wino.hip), 8188 / 4094 for the attention operands q / kv (attn.hip).
+  // Always-on saturation watch (the engine's counter; in the op entry points what pf_op_set_saturation_watch set, nullptr by default): every producer of a tensor that a
+  // split-f16 contraction will read counts the 16-byte groups of its output with an element beyond sat_limit (or NaN) into *sat -- one compare per group and, in a
+  // healthy network, no atomic ever.  The limit is the CONSUMER's window: 65504, 65504 / 4 in front of a Winograd conv (wino.hip), 8188 / 4094 for the attention
+  // operands q / kv (attn.hip).  A split-K launch is watched by its reduce kernel (igemm_sb.hip splitk_reduce_kernel), which writes the finished output.
   unsigned* sat = nullptr;
   float sat_limit = 65504.f;
   int wino_half = 1;  // Winograd launches: non-zero = the half-patch geometry where it applies (wino.hip), 0 = square patches always (PF_WINO_HALF: the engine sets what its
@@ -342,9 +343,7 @@ struct RbLinArgs {
   float* y;                  // [M][N]
   int M, tokens, bpi;        // rows, tokens per image, blocks per image = ceil(tokens / 64)
   int N, act;
-  // Always-on saturation watch (engine only; nullptr in the op entry points): every producer of a tensor that a split-f16 contraction will read counts the 16-byte
-  // groups of its output with an element beyond sat_limit (or NaN) into *sat -- one compare per group and, in a healthy network, no atomic ever.  The limit is the
-  // CONSUMER's window: 65504, 65504 / 4 in front of a Winograd conv (wino.hip), 8188 / 4094 for the attention operands q / kv (attn.hip).
+  // saturation watch of y against sat_limit (ConvParams::sat)
   unsigned* sat = nullptr;
   float sat_limit = 65504.f;
   unsigned long long* stamps = nullptr;  // timing aid (scripts/tune_rb.py, PF_RB_STAMPS=1): s_memtime stamps of block 17, [wave][64]
@@ -375,7 +374,8 @@ struct RbProjFc1Args {
   const float* fc1_inv; const float* fc1_bias;     // [4 C]
   float* hidden;              // [M][4 C]
   int B, tokens, bpi;         // bpi = ceil(tokens / 64)
-  unsigned* sat = nullptr;    // saturation watch of x1 and hidden (ConvParams::sat)
+  unsigned* sat = nullptr;    // saturation watch of x1 (against sat_limit) and hidden (against hidden_limit: the depthwise conv's input window), ConvParams::sat
+  float sat_limit = 65504.f, hidden_limit = 65504.f;
 };
 void launch_rb_proj_fc1(const RbProjFc1Args& a, int C, hipStream_t s);
 void launch_rb_srkv(const RbSrKvArgs& a, int C, hipStream_t s);

@@ -333,7 +333,10 @@ __global__ __launch_bounds__(256, 1) void rb_proj_fc1_kernel(const RbProjFc1Args
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int ml = rt * 32 + rrow + 8 * i;
-        if (ml < nrows) *reinterpret_cast<float4*>(p.x + (size_t)(m0 + ml) * C + ct * 32 + c4 * 4) = v[i];
+        if (ml < nrows) {
+          if (p.sat) sat_watch4(p.sat, p.sat_limit, v[i].x, v[i].y, v[i].z, v[i].w);  // x1 is read raw by the next block's LayerNorm-fused layers
+          *reinterpret_cast<float4*>(p.x + (size_t)(m0 + ml) * C + ct * 32 + c4 * 4) = v[i];
+        }
       }
     }
   }
@@ -397,7 +400,7 @@ __global__ __launch_bounds__(256, 1) void rb_proj_fc1_kernel(const RbProjFc1Args
         rb_step<G>(acc, W, d, A[d & 1], A[(d + 1) & 1], As + nx * G::CHS, lane, xr);
       }
     }
-    rb_chain_epilogue_store<G, false, ACT_NONE>(p.hidden, H4, tabs + 2 * C, tabs + 2 * C + H4, escr + wave * 1024, acc, ps2 * G::COLS, m0, nrows, wave, lane, p.sat);
+    rb_chain_epilogue_store<G, false, ACT_NONE>(p.hidden, H4, tabs + 2 * C, tabs + 2 * C + H4, escr + wave * 1024, acc, ps2 * G::COLS, m0, nrows, wave, lane, p.sat, p.hidden_limit);
   }
 }
 

@@ -77,6 +77,7 @@ _SIGNATURES = {
     "pf_debug_forward_u8": (_c.c_int, [_P, _c.c_int, _P, _P, _P, _P, _P, _c.c_size_t, _c.c_int, _P, _c.c_size_t, _P]),
     "pf_debug_taps": (_c.c_int, [_P, _c.c_int, _P, _c.POINTER(_c.c_longlong), _c.POINTER(_c.c_int)]),
     "pf_debug_ranges": (_c.c_int, [_P, _c.c_int, _P, _c.POINTER(_c.c_longlong), _c.POINTER(_c.c_float)]),
+    "pf_op_set_saturation_watch": (_c.c_int, [_P, _c.c_float]),
     "pf_op_conv2d": (_c.c_int, [_c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P,
                                 _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_int,
                                 _c.c_int, _c.c_int, _P, _P, _c.c_long, _P, _c.c_long, _P, _c.c_long, _c.c_int, _P]),

@@ -3,6 +3,7 @@ and tuning.  Activations are NHWC float32 torch tensors on a GPU; weights are pa
 reference's (PyTorch) layouts and packed by the library."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -23,6 +24,21 @@ def _hp(a):
 
 def _dp(t):
     return t.data_ptr() if t is not None else None
+
+
+@contextlib.contextmanager
+def saturation_watch(limit=65504.0):
+    """Switches the saturation watch of the kernel-level entry points on for this thread (pf_op_set_saturation_watch): yields a zeroed uint32 device counter
+    (a one-element int32 tensor on the current device) that every pf_op_* launch inside the block adds to when an output leaves `limit`; always off again afterwards."""
+    import torch
+
+    lib = load_library()
+    counter = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
+    _check(lib.pf_op_set_saturation_watch(counter.data_ptr(), float(limit)), None, "pf_op_set_saturation_watch")
+    try:
+        yield counter
+    finally:
+        lib.pf_op_set_saturation_watch(None, 0.0)
 
 
 class Planes:
