@@ -356,6 +356,32 @@ int pf_fit_camera_usm(int device, int batch, const int32_t* h_hw, const float* c
                       const float* d_init /* NULL or [B][6] */, int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat,
                       int max_iter, float* d_out /* [B][PF_USMFIT_COLS] */, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* The two fits above with the intrinsics shared across the images of one camera: the frames of a video, a photo set
+ * of one device.  The batch is divided into camera groups of consecutive images: h_group_sizes = HOST [n_groups], every entry >= 1, summing to
+ * batch.  Every image keeps its own roll and pitch; all images of a group share f, with free_pp = 1 also cx and cy, with model = 1 also xi.
+ * model = 0: the pinhole fit (theta [5], rows of PF_FIT_COLS); 1: the USM fit (theta [6], rows of PF_USMFIT_COLS).  Model, residuals, loss,
+ * weights and clamps per image: as pf_fit_camera / pf_fit_camera_usm; the objective of a group is the sum over its images.
+ * One Levenberg-Marquardt iteration of a group, with H_i = [A_i B_i; B_i^T C_i] and g_i = (g_a, g_s) the normal matrix and gradient of image i,
+ * A_i its 2 x 2 (roll, pitch) block and C_i the block of the NS shared parameters -- the whole block-arrow system is damped, then every A_i eliminated:
+ *   A'_i = A_i + lambda diag A_i, C' = sum C_i + lambda diag(sum C_i), S = C' - sum B_i^T A'_i^-1 B_i, b = sum (g_s - B_i^T A'_i^-1 g_a)
+ *   delta_s = -S^-1 b (Cholesky, fp64), delta_a_i = -A'_i^-1 (g_a + B_i delta_s)
+ * One lambda per group; a trial is accepted when the cost summed over the group falls, otherwise lambda x 10 with the same linearisation.
+ * Stopping: the constants of pf_fit_camera on the group's cost and longest step; all images of a group stop together.
+ * Start: that of the per-image fit for every image (blind, or d_init = DEVICE [B][5 or 6]), then per group f = exp(mean log f) and cx, cy, xi =
+ * the means over its images.  An image without a valid pixel contributes nothing to the steps: its row keeps its start roll and pitch,
+ * VALID_PIXELS 0 and CONVERGED 0, and follows the group's shared parameters.  A group without any valid pixel keeps its start, CONVERGED 0.
+ * d_out row of an image: its own roll and pitch; the group's f / cx / cy / xi (the same bits in every row of the group) and what derives from
+ * them; its own RMS_*, COST and VALID_PIXELS; the group's ITERATIONS and CONVERGED.  The group's cost is the sum of its rows' COST.
+ * All images of a group must have one size (rel_focal is relative to the height); sizes may differ between groups.  Argument checks
+ * (PF_ERR_ARG before any device work): those of pf_fit_camera, model, the group sizes and their sum, one size per group.
+ * pf_fit_camera_shared_workspace_bytes is 0 for batch <= 0, a size below 8, a model outside {0, 1} or bad group sizes.
+ * Enqueues per iteration (max_iter + 1 of them) one (accumulate, reduce) launch pair per 32 images and one solve launch per 128 groups on
+ * `stream`, no host synchronisation, no atomics; a group's bits depend on its own images only, not on its place in the batch. */
+size_t pf_fit_camera_shared_workspace_bytes(int model, int batch, const int32_t* h_hw, int n_groups, const int32_t* h_group_sizes);
+int pf_fit_camera_shared(int device, int model, int batch, const int32_t* h_hw, const float* const* h_up, const float* const* h_lat, int n_groups,
+                         const int32_t* h_group_sizes, const float* d_init, int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat,
+                         int max_iter, float* d_out, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* The forward direction of that model: d_cam6 = {roll, pitch (RADIANS), rel_focal, rel_cx, rel_cy, xi} in device memory -> d_up [2][H][W],
  * d_lat [H][W] degrees; NaN where a point has no ray (xi > 1).  xi == 0 gives the bits of pf_fields_from_params; otherwise pf_pano_crop's
  * label formulas.  xi is read on the device, so a fitted xi feeds it without a host round trip.  Stateless, no handle. */

@@ -2169,34 +2169,30 @@ static size_t fit_workspace_bytes(const FitKind& fk, int B, const int32_t* hw) {
   return n;
 }
 
-static int fit_camera_run(const FitKind& fk, int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init,
-                          int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes,
-                          void* stream) {
-  if (B <= 0 || !hw || !up || !lat || !d_out) { g_create_error = fmt("%s: bad argument", fk.name); return PF_ERR_ARG; }
+// the argument checks every camera fit makes before any device work; PF_OK or PF_ERR_ARG with g_create_error set
+static int fit_check_args(const char* name, int B, const int32_t* hw, const float* const* up, const float* const* lat, int free_pp, int loss,
+                          float huber_delta_deg, float w_up, float w_lat, int max_iter, const float* d_out) {
+  if (B <= 0 || !hw || !up || !lat || !d_out) { g_create_error = fmt("%s: bad argument", name); return PF_ERR_ARG; }
   if ((free_pp != 0 && free_pp != 1) || (loss != PF_FIT_LOSS_L2 && loss != PF_FIT_LOSS_HUBER) || max_iter < 1 || max_iter > 1000) {
-    g_create_error = fmt("%s: bad option (free_pp %d, loss %d, max_iter %d)", fk.name, free_pp, loss, max_iter);
+    g_create_error = fmt("%s: bad option (free_pp %d, loss %d, max_iter %d)", name, free_pp, loss, max_iter);
     return PF_ERR_ARG;
   }
   if (!(w_up >= 0.f && w_lat >= 0.f && std::isfinite(w_up) && std::isfinite(w_lat) && w_up + w_lat > 0.f) ||
       (loss == PF_FIT_LOSS_HUBER && !(huber_delta_deg > 0.f && std::isfinite(huber_delta_deg)))) {
-    g_create_error = fmt("%s: weights must be finite, >= 0 and not both 0; huber_delta_deg must be finite and > 0", fk.name);
+    g_create_error = fmt("%s: weights must be finite, >= 0 and not both 0; huber_delta_deg must be finite and > 0", name);
     return PF_ERR_ARG;
   }
   for (int i = 0; i < B; ++i) {
-    if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) { g_create_error = fmt("%s: image %d is %d x %d, smaller than 8 x 8", fk.name, i, hw[2 * i], hw[2 * i + 1]); return PF_ERR_ARG; }
-    if (!up[i] || !lat[i]) { g_create_error = fmt("%s: NULL field pointer of image %d", fk.name, i); return PF_ERR_ARG; }
+    if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) { g_create_error = fmt("%s: image %d is %d x %d, smaller than 8 x 8", name, i, hw[2 * i], hw[2 * i + 1]); return PF_ERR_ARG; }
+    if (!up[i] || !lat[i]) { g_create_error = fmt("%s: NULL field pointer of image %d", name, i); return PF_ERR_ARG; }
   }
-  const size_t need = fit_workspace_bytes(fk, B, hw);
-  if (!ws || ws_bytes < need) { g_create_error = fmt("%s: needs %zu workspace bytes, got %zu", fk.name, need, ws_bytes); return PF_ERR_WORKSPACE; }
-  std::string err;
-  const int rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-  double* state = reinterpret_cast<double*>(base);
-  char* part = base + fit_state_bytes(fk, B);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat};
-  std::vector<FitBatch> groups;
+  return PF_OK;
+}
+
+// the launch groups of a batch: FitBatch::MAX images each, their partial records laid out one after the other from `part`
+static std::vector<FitBatch> fit_batches(const FitKind& fk, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init,
+                                         double* state, char* part, float* d_out) {
+  std::vector<FitBatch> batches;
   for (int i0 = 0; i0 < B; i0 += FitBatch::MAX) {
     FitBatch fb;
     fb.n = std::min(B - i0, (int)FitBatch::MAX);
@@ -2210,8 +2206,25 @@ static int fit_camera_run(const FitKind& fk, int device, int B, const int32_t* h
     fb.state = state + (size_t)i0 * fk.state;
     fb.out = d_out + (size_t)i0 * fk.cols;
     fb.init = d_init ? d_init + (size_t)i0 * fk.ntheta : nullptr;
-    groups.push_back(fb);
+    batches.push_back(fb);
   }
+  return batches;
+}
+
+static int fit_camera_run(const FitKind& fk, int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init,
+                          int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes,
+                          void* stream) {
+  int rc = fit_check_args(fk.name, B, hw, up, lat, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out);
+  if (rc != PF_OK) return rc;
+  const size_t need = fit_workspace_bytes(fk, B, hw);
+  if (!ws || ws_bytes < need) { g_create_error = fmt("%s: needs %zu workspace bytes, got %zu", fk.name, need, ws_bytes); return PF_ERR_WORKSPACE; }
+  std::string err;
+  rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat};
+  const std::vector<FitBatch> groups = fit_batches(fk, B, hw, up, lat, d_init, reinterpret_cast<double*>(base), base + fit_state_bytes(fk, B), d_out);
   // no host synchronisation: every image stops on its own flag, the launches run out as no-ops
   for (const FitBatch& fb : groups) fk.init(fb, prm, s);
   for (int it = 0; it <= max_iter; ++it)
@@ -2232,6 +2245,90 @@ size_t pf_fit_camera_usm_workspace_bytes(int B, const int32_t* hw) { return fit_
 int pf_fit_camera_usm(int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int loss,
                       float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes, void* stream) {
   return fit_camera_run(kFitUsm, device, B, hw, up, lat, d_init, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out, ws, ws_bytes, stream);
+}
+
+// pf_fit_camera_shared: the per-image fits' init and accumulate kernels over launch groups of FitBatch::MAX images, and per iteration one
+// reduction per image and one solve per camera group (fit_lm.h).  Workspace: that of the per-image fit, then the [B][rec] summed records.
+struct FitSharedKind {
+  const FitKind& fk;
+  void (*start)(const FitGroups&, hipStream_t);
+  void (*accum)(const FitBatch&, const FitParams&, double*, hipStream_t);
+  void (*solve)(const FitGroups&, const FitParams&, hipStream_t);
+};
+static const FitSharedKind kFitShared[2] = {
+    {kFitPinhole, launch_fit_shared_start<PinholeFit>, launch_fit_shared_accum<PinholeFit>, launch_fit_shared_solve<PinholeFit>},
+    {kFitUsm, launch_fit_shared_start<UsmFit>, launch_fit_shared_accum<UsmFit>, launch_fit_shared_solve<UsmFit>}};
+static size_t fit_rec_bytes(const FitKind& fk, int B) { return ((size_t)B * fk.rec * sizeof(double) + 255) & ~(size_t)255; }
+
+// group sizes: every entry >= 1, summing to B
+static bool fit_groups_ok(int B, int n_groups, const int32_t* gs, std::string* why) {
+  if (n_groups < 1 || !gs) { *why = fmt("bad group sizes (n_groups %d)", n_groups); return false; }
+  long sum = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    if (gs[g] < 1) { *why = fmt("bad group sizes (group %d has %d images)", g, gs[g]); return false; }
+    sum += gs[g];
+  }
+  if (sum != B) { *why = fmt("the group sizes sum to %ld, the batch is %d", sum, B); return false; }
+  return true;
+}
+
+size_t pf_fit_camera_shared_workspace_bytes(int model, int B, const int32_t* hw, int n_groups, const int32_t* group_sizes) {
+  std::string why;
+  if ((model != 0 && model != 1) || B <= 0 || !fit_groups_ok(B, n_groups, group_sizes, &why)) return 0;
+  const FitKind& fk = kFitShared[model].fk;
+  const size_t n = fit_workspace_bytes(fk, B, hw);
+  return n ? n + fit_rec_bytes(fk, B) : 0;
+}
+
+int pf_fit_camera_shared(int device, int model, int B, const int32_t* hw, const float* const* up, const float* const* lat, int n_groups,
+                         const int32_t* group_sizes, const float* d_init, int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter,
+                         float* d_out, void* ws, size_t ws_bytes, void* stream) {
+  const char* name = "pf_fit_camera_shared";
+  if (model != 0 && model != 1) { g_create_error = fmt("%s: model must be 0 (pinhole) or 1 (USM), got %d", name, model); return PF_ERR_ARG; }
+  int rc = fit_check_args(name, B, hw, up, lat, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out);
+  if (rc != PF_OK) return rc;
+  std::string why;
+  if (!fit_groups_ok(B, n_groups, group_sizes, &why)) { g_create_error = fmt("%s: %s", name, why.c_str()); return PF_ERR_ARG; }
+  for (int g = 0, i0 = 0; g < n_groups; i0 += group_sizes[g], ++g) {
+    for (int i = i0 + 1; i < i0 + group_sizes[g]; ++i) {
+      if (hw[2 * i] != hw[2 * i0] || hw[2 * i + 1] != hw[2 * i0 + 1]) {
+        g_create_error = fmt("%s: the images of a group must have one size (rel_focal is relative to the height): group %d has %d x %d and %d x %d", name, g,
+                             hw[2 * i0], hw[2 * i0 + 1], hw[2 * i], hw[2 * i + 1]);
+        return PF_ERR_ARG;
+      }
+    }
+  }
+  const FitSharedKind& sk = kFitShared[model];
+  const FitKind& fk = sk.fk;
+  const size_t need = fit_workspace_bytes(fk, B, hw) + fit_rec_bytes(fk, B);
+  if (!ws || ws_bytes < need) { g_create_error = fmt("%s: needs %zu workspace bytes, got %zu", name, need, ws_bytes); return PF_ERR_WORKSPACE; }
+  std::string err;
+  rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+  double* state = reinterpret_cast<double*>(base);
+  double* rec = reinterpret_cast<double*>(base + fit_state_bytes(fk, B));
+  char* part = base + fit_state_bytes(fk, B) + fit_rec_bytes(fk, B);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat};
+  const std::vector<FitBatch> batches = fit_batches(fk, B, hw, up, lat, d_init, state, part, d_out);
+  std::vector<FitGroups> groups;
+  for (int g0 = 0, i0 = 0; g0 < n_groups; g0 += FitGroups::MAX) {
+    FitGroups fg;
+    fg.n = std::min(n_groups - g0, (int)FitGroups::MAX);
+    for (int k = 0; k < fg.n; ++k) { fg.start[k] = i0; fg.size[k] = group_sizes[g0 + k]; i0 += group_sizes[g0 + k]; }
+    fg.state = state; fg.rec = rec; fg.out = d_out;
+    groups.push_back(fg);
+  }
+  // no host synchronisation: every group stops on its own flag, the launches run out as no-ops
+  for (const FitBatch& fb : batches) fk.init(fb, prm, s);
+  for (const FitGroups& fg : groups) sk.start(fg, s);
+  for (int it = 0; it <= max_iter; ++it) {
+    for (size_t k = 0; k < batches.size(); ++k) sk.accum(batches[k], prm, rec + k * FitBatch::MAX * fk.rec, s);
+    for (const FitGroups& fg : groups) sk.solve(fg, prm, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = fmt("%s: kernel launch failed", name); return PF_ERR_DEVICE; }
+  return PF_OK;
 }
 
 int pf_fields_from_params_usm(int device, const float* d_cam6, int H, int W, float* d_up, float* d_lat, void* stream) {

@@ -137,5 +137,8 @@ struct PinholeFit {
 
 template void launch_fit_init<PinholeFit>(const FitBatch&, const FitParams&, hipStream_t);
 template void launch_fit_iteration<PinholeFit>(const FitBatch&, const FitParams&, hipStream_t);
+template void launch_fit_shared_start<PinholeFit>(const FitGroups&, hipStream_t);
+template void launch_fit_shared_accum<PinholeFit>(const FitBatch&, const FitParams&, double*, hipStream_t);
+template void launch_fit_shared_solve<PinholeFit>(const FitGroups&, const FitParams&, hipStream_t);
 
 }  // namespace pf

@@ -219,6 +219,9 @@ struct UsmFit {
 
 template void launch_fit_init<UsmFit>(const FitBatch&, const FitParams&, hipStream_t);
 template void launch_fit_iteration<UsmFit>(const FitBatch&, const FitParams&, hipStream_t);
+template void launch_fit_shared_start<UsmFit>(const FitGroups&, hipStream_t);
+template void launch_fit_shared_accum<UsmFit>(const FitBatch&, const FitParams&, double*, hipStream_t);
+template void launch_fit_shared_solve<UsmFit>(const FitGroups&, const FitParams&, hipStream_t);
 
 // ---------------------------------------------------------------- theta -> fields
 // One thread per 4 consecutive pixels of the flattened image.  xi == 0: pinhole_fields_at, the bits of pf_fields_from_params;

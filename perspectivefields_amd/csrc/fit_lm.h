@@ -6,6 +6,12 @@
 //                               (no atomics: the result is the same on every run and does not depend on the batch an image is in)
 //   fit_solve_kernel<Fit, NP>   one wave per image: partials summed in a fixed order in fp64, LM accept / reject, damped
 //                               Cholesky solve in fp64, next trial parameters, per-image convergence flag, output row
+// The fit with intrinsics shared across the images of a camera group (pf_fit_camera_shared) keeps init and accumulate
+// and replaces the solve by a pair, because a group may hold any number of images anywhere in the batch:
+//   fit_shared_start_kernel<Fit>       one wave per group, after init: the group's f = exp(mean log f), cx, cy, xi = the means of its members' starts
+//   fit_shared_reduce_kernel<Fit, NP>  one wave per image: the partials summed as fit_solve_kernel sums them -> rec [B][Fit::REC]
+//   fit_shared_solve_kernel<Fit, NP>   one wave per group: accept / reject on the group's cost, every member's 2 x 2 (roll, pitch) block eliminated
+//                                      from the damped block-arrow system, the shared NP - 2 parameters by Cholesky in fp64, back-substitution
 // A model is a traits type Fit in namespace pf (it is part of the kernels' names) with
 //   NTH, STATE, REC, COLS       parameters in theta; doubles of one image's state and of one partial record; floats of an output row
 //   theta_of<NP>(k)             place in theta of free parameter k of the NP-parameter fit
@@ -51,8 +57,9 @@ struct St {
                        CONV = COST + 3,         // 0: running; 1: converged; 2: no finite cost at the start.  Accumulate and solve return at once when != 0
                        UP2 = COST + 4, LAT2 = COST + 5, CNT = COST + 6,  // rms sums and valid pixels at CUR
                        HG = COST + 7,           // [NH + NP] J^T W J and J^T W r at CUR
-                       END = HG + Rec<Fit::NTH>::NH + Fit::NTH;
-  static_assert(END <= Fit::STATE, "state too small");
+                       END = HG + Rec<Fit::NTH>::NH + Fit::NTH,
+                       GCONV = END;             // shared fit only: the group's flag, the same in every member (CONV of a member without a valid pixel stays 2)
+  static_assert(GCONV < Fit::STATE, "state too small");
   static_assert(Rec<Fit::NTH>::NV <= Fit::REC, "record too small");
 };
 
@@ -343,6 +350,305 @@ __global__ __launch_bounds__(64) void fit_solve_kernel(const FitBatch fb) {
   write_out<Fit>(fb.out + (long)img * Fit::COLS, st);
 }
 
+// ================================================================ intrinsics shared across the images of a group
+// place of element (i, j), i <= j, in the row-by-row upper triangle of an NP x NP matrix
+template <int NP>
+__device__ __forceinline__ constexpr int tri(int i, int j) { return i * NP - i * (i - 1) / 2 + (j - i); }
+
+// ---------------------------------------------------------------- group start: one wave per group
+template <class Fit>
+__global__ __launch_bounds__(64) void fit_shared_start_kernel(const FitGroups fg) {
+  using S = St<Fit>;
+  constexpr int NTH = Fit::NTH, NS = NTH - 2;
+  const int g = blockIdx.x, lane = threadIdx.x;
+  if (g >= fg.n) return;
+  const int i0 = fg.start[g], n = fg.size[g];
+  __shared__ double red[64][NS];
+  double acc[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) acc[k] = 0.0;
+  for (int i = lane; i < n; i += 64) {
+    const double* st = fg.state + (long)(i0 + i) * Fit::STATE;
+    acc[0] += log(st[S::CUR + 2]);
+#pragma unroll
+    for (int k = 1; k < NS; ++k) acc[k] += st[S::CUR + 2 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < NS; ++k) red[lane][k] = acc[k];
+  __syncthreads();
+  // every lane adds the 64 lane sums in lane order: the same bits in all of them
+  double sh[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    double s = 0.0;
+    for (int l = 0; l < 64; ++l) s += red[l][k];
+    sh[k] = s / (double)n;
+  }
+  sh[0] = exp(sh[0]);
+  for (int i = lane; i < n; i += 64) {
+    double* st = fg.state + (long)(i0 + i) * Fit::STATE;
+    double th[NTH];
+    th[0] = st[S::CUR];
+    th[1] = st[S::CUR + 1];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) th[2 + k] = sh[k];
+    Fit::clamp_theta(th);
+    for (int k = 0; k < NTH; ++k) { st[S::CUR + k] = th[k]; st[S::TRIAL + k] = th[k]; }
+    st[S::GCONV] = 0.0;
+    write_out<Fit>(fg.out + (long)(i0 + i) * Fit::COLS, st);
+  }
+}
+
+// ---------------------------------------------------------------- per-image reduction: one wave per image
+template <class Fit, int NP>
+__global__ __launch_bounds__(64) void fit_shared_reduce_kernel(const FitBatch fb, double* __restrict__ rec) {
+  using R = Rec<NP>;
+  using S = St<Fit>;
+  const int img = blockIdx.x, lane = threadIdx.x;
+  if (img >= fb.n) return;
+  if (fb.state[(long)img * Fit::STATE + S::CONV] != 0.0) return;
+  if (lane < R::NV) {
+    // 8 loads in flight, added in block order (as fit_solve_kernel)
+    const double* part = fb.part[img] + lane;
+    const int nb = fb.nblk[img];
+    double s = 0.0;
+    for (int b0 = 0; b0 < nb; b0 += 8) {
+      double v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = b0 + k < nb ? part[(long)(b0 + k) * Fit::REC] : 0.0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) s += v[k];
+    }
+    rec[(long)img * Fit::REC + lane] = s;
+  }
+}
+
+// (A + lambda diag A)^-1 of a member's (roll, pitch) block as (i00, i01, i11); false when the damped block is not positive definite
+template <int NP>
+__device__ __forceinline__ bool inv_own_block(const double* hg, double lambda, double* inv) {
+  const double a00 = hg[tri<NP>(0, 0)] * (1.0 + lambda), a01 = hg[tri<NP>(0, 1)], a11 = hg[tri<NP>(1, 1)] * (1.0 + lambda);
+  const double det = a00 * a11 - a01 * a01;
+  const bool pd = a00 > 0.0 && det > 0.0;
+  const double r = 1.0 / (pd ? det : 1.0);
+  inv[0] = a11 * r;
+  inv[1] = -(a01 * r);
+  inv[2] = a00 * r;
+  return pd;
+}
+
+// ---------------------------------------------------------------- shared solve: one wave per group
+// Lane l owns members l, l + 64, ...  Sums over the group: per lane in member order, then over the lanes in lane order, in fp64 -- the
+// bits of a group depend on nothing but its own members.  What follows a group sum is computed by every lane from the same numbers.
+template <class Fit, int NP>
+__global__ __launch_bounds__(64) void fit_shared_solve_kernel(const FitGroups fg) {
+  using R = Rec<NP>;
+  using S = St<Fit>;
+  constexpr int NTH = Fit::NTH, NS = NP - 2, NT = NS * (NS + 1) / 2;
+  constexpr int RT = 0, RD = NT, RB = NT + NS, RBAD = NT + 2 * NS, NRED = RBAD + 1;  // C - B^T A^-1 B, diag C, b, members with a singular block
+  static_assert(NRED >= 3 && NRED <= 64, "reduction width");
+  const int g = blockIdx.x, lane = threadIdx.x;
+  if (g >= fg.n) return;
+  const int i0 = fg.start[g], n = fg.size[g];
+  double* const st0 = fg.state + (long)i0 * Fit::STATE;
+  if (st0[S::GCONV] != 0.0) return;  // the whole block
+  const int nev = (int)st0[S::NEV];
+  double lambda = st0[S::LAMBDA];
+  __shared__ double red[64][NRED];
+  __shared__ double tot[NRED];
+
+  // ---- the group's cost at the trial and at the accepted parameters; at the first evaluation, the members without a valid pixel leave
+  double acc[NRED];
+#pragma unroll
+  for (int k = 0; k < NRED; ++k) acc[k] = 0.0;
+  for (int i = lane; i < n; i += 64) {
+    double* st = fg.state + (long)(i0 + i) * Fit::STATE;
+    const double* rc = fg.rec + (long)(i0 + i) * Fit::REC;
+    if (nev == 0 && !(rc[R::CNT] > 0.0 && isfinite(rc[R::COST]))) {
+      st[S::CONV] = 2.0;
+      st[S::COST] = rc[R::COST];
+      st[S::CNT] = rc[R::CNT];
+    }
+    if (st[S::CONV] != 0.0) continue;
+    acc[0] += rc[R::COST];
+    acc[1] += st[S::COST];
+    acc[2] += 1.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) red[lane][k] = acc[k];
+  __syncthreads();
+  if (lane < 3) {
+    double s = 0.0;
+    for (int l = 0; l < 64; ++l) s += red[l][lane];
+    tot[lane] = s;
+  }
+  __syncthreads();
+  const double cost_t = tot[0], cost_c = tot[1];
+  const bool any = tot[2] > 0.0;
+  __syncthreads();  // tot and red are written again below
+  const bool accept = any && isfinite(cost_t) && (nev == 0 || cost_t < cost_c);
+  double conv = 0.0;
+  if (accept) {
+    if (nev > 0) {
+      if (cost_c - cost_t <= 1e-10 * cost_c) conv = 1.0;
+      lambda = fmax(lambda * 0.1, 1e-12);
+    }
+    if (cost_t == 0.0) conv = 1.0;
+  } else if (nev == 0) {
+    conv = 2.0;  // no member has a valid pixel: every output row keeps the start parameters
+  } else {  // reject: more damping, same linearisation
+    lambda *= 10.0;
+    if (lambda > 1e16) conv = 1.0;
+  }
+
+  // ---- accept, then every member's (roll, pitch) block out of the damped system
+#pragma unroll
+  for (int k = 0; k < NRED; ++k) acc[k] = 0.0;
+  for (int i = lane; i < n; i += 64) {
+    double* st = fg.state + (long)(i0 + i) * Fit::STATE;
+    const bool live = st[S::CONV] == 0.0;
+    if (accept) {
+      for (int k = 0; k < NTH; ++k) st[S::CUR + k] = st[S::TRIAL + k];  // a member without a valid pixel follows the group's shared parameters
+      if (live) {
+        const double* rc = fg.rec + (long)(i0 + i) * Fit::REC;
+        for (int k = 0; k < R::NH + NP; ++k) st[S::HG + k] = rc[k];
+        st[S::COST] = rc[R::COST];
+        st[S::UP2] = rc[R::UP2];
+        st[S::LAT2] = rc[R::LAT2];
+        st[S::CNT] = rc[R::CNT];
+      }
+    }
+    if (!live || conv != 0.0) continue;
+    const double* hg = st + S::HG;
+    double inv[3];
+    if (!inv_own_block<NP>(hg, lambda, inv)) acc[RBAD] += 1.0;
+    const double ga0 = hg[R::NH], ga1 = hg[R::NH + 1];
+    const double v0 = inv[0] * ga0 + inv[1] * ga1, v1 = inv[1] * ga0 + inv[2] * ga1;  // A^-1 g_a
+    double B0[NS], B1[NS], w0[NS], w1[NS];                                           // B, A^-1 B
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      B0[k] = hg[tri<NP>(0, 2 + k)];
+      B1[k] = hg[tri<NP>(1, 2 + k)];
+      w0[k] = inv[0] * B0[k] + inv[1] * B1[k];
+      w1[k] = inv[1] * B0[k] + inv[2] * B1[k];
+    }
+    int t = 0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+#pragma unroll
+      for (int l = k; l < NS; ++l, ++t) acc[RT + t] += hg[tri<NP>(2 + k, 2 + l)] - (B0[k] * w0[l] + B1[k] * w1[l]);
+      acc[RD + k] += hg[tri<NP>(2 + k, 2 + k)];
+      acc[RB + k] += hg[R::NH + 2 + k] - (B0[k] * v0 + B1[k] * v1);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NRED; ++k) red[lane][k] = acc[k];
+  __syncthreads();
+  if (lane < NRED) {
+    double s = 0.0;
+    for (int l = 0; l < 64; ++l) s += red[l][lane];
+    tot[lane] = s;
+  }
+  __syncthreads();
+
+  // ---- S delta_s = -b by Cholesky in fp64, S = sum (C - B^T A^-1 B) + lambda diag(sum C)
+  double ds[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) ds[k] = 0.0;
+  if (conv == 0.0) {
+    double A[NS][NS];
+    int t = 0;
+#pragma unroll
+    for (int i = 0; i < NS; ++i)
+#pragma unroll
+      for (int j = i; j < NS; ++j) { A[i][j] = tot[RT + t]; A[j][i] = tot[RT + t]; ++t; }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) { A[i][i] += lambda * tot[RD + i]; ds[i] = -tot[RB + i]; }
+    bool pd = tot[RBAD] == 0.0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      double d = A[j][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
+      pd = pd && d > 0.0;
+      d = sqrt(fmax(d, 1e-300));
+      A[j][j] = d;
+#pragma unroll
+      for (int i = j + 1; i < NS; ++i) {
+        double v = A[i][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) v -= A[i][k] * A[j][k];
+        A[i][j] = v / d;
+      }
+    }
+    if (!pd) {
+      conv = 1.0;  // singular normal equations: the data determine no step
+    } else {
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+        double v = ds[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v -= A[i][k] * ds[k];
+        ds[i] = v / A[i][i];
+      }
+#pragma unroll
+      for (int i = NS - 1; i >= 0; --i) {
+        double v = ds[i];
+#pragma unroll
+        for (int k = i + 1; k < NS; ++k) v -= A[k][i] * ds[k];
+        ds[i] = v / A[i][i];
+      }
+    }
+  }
+
+  // ---- back-substitution: delta_a = -A^-1 (g_a + B delta_s); next trial parameters; the group's longest step
+  double step = 0.0;
+  if (conv == 0.0) {
+    for (int i = lane; i < n; i += 64) {
+      double* st = fg.state + (long)(i0 + i) * Fit::STATE;
+      const bool live = st[S::CONV] == 0.0;
+      double th[NTH];
+      for (int k = 0; k < NTH; ++k) th[k] = st[S::CUR + k];
+      if (live) {
+        const double* hg = st + S::HG;
+        double inv[3];
+        inv_own_block<NP>(hg, lambda, inv);
+        double r0 = hg[R::NH], r1 = hg[R::NH + 1];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+          r0 += hg[tri<NP>(0, 2 + k)] * ds[k];
+          r1 += hg[tri<NP>(1, 2 + k)] * ds[k];
+        }
+        th[Fit::template theta_of<NP>(0)] -= inv[0] * r0 + inv[1] * r1;
+        th[Fit::template theta_of<NP>(1)] -= inv[1] * r0 + inv[2] * r1;
+      }
+#pragma unroll
+      for (int k = 0; k < NS; ++k) th[Fit::template theta_of<NP>(2 + k)] += ds[k];
+      Fit::clamp_theta(th);
+      for (int k = 0; k < NTH; ++k) {
+        if (live) step = fmax(step, fabs(th[k] - st[S::CUR + k]));
+        st[S::TRIAL + k] = th[k];
+      }
+    }
+  }
+  red[lane][0] = step;
+  __syncthreads();
+  if (conv == 0.0) {
+    double m = 0.0;
+    for (int l = 0; l < 64; ++l) m = fmax(m, red[l][0]);
+    if (m < 1e-9) conv = 1.0;
+  }
+
+  // ---- state and output rows
+  for (int i = lane; i < n; i += 64) {
+    double* st = fg.state + (long)(i0 + i) * Fit::STATE;
+    st[S::LAMBDA] = lambda;
+    st[S::NEV] = (double)(nev + 1);
+    st[S::GCONV] = conv;
+    if (st[S::CONV] == 0.0) st[S::CONV] = conv;
+    write_out<Fit>(fg.out + (long)(i0 + i) * Fit::COLS, st);
+  }
+}
+
 // ---------------------------------------------------------------- launchers (declared in pf_kernels.h; each model's unit instantiates its pair)
 template <class Fit>
 void launch_fit_init(const FitBatch& fb, const FitParams& prm, hipStream_t s) {
@@ -361,6 +667,33 @@ void launch_fit_iteration(const FitBatch& fb, const FitParams& prm, hipStream_t 
     hipLaunchKernelGGL((fit_accum_kernel<Fit, Fit::NTH - 2>), dim3(mx, fb.n), dim3(256), 0, s, fb, prm);
     hipLaunchKernelGGL((fit_solve_kernel<Fit, Fit::NTH - 2>), dim3(fb.n), dim3(64), 0, s, fb);
   }
+}
+
+template <class Fit>
+void launch_fit_shared_start(const FitGroups& fg, hipStream_t s) {
+  hipLaunchKernelGGL(fit_shared_start_kernel<Fit>, dim3(fg.n), dim3(64), 0, s, fg);
+}
+
+// the existing accumulate kernel, then the per-image reduction into rec (this launch group's first record)
+template <class Fit>
+void launch_fit_shared_accum(const FitBatch& fb, const FitParams& prm, double* rec, hipStream_t s) {
+  int mx = 1;
+  for (int k = 0; k < fb.n; ++k) mx = std::max(mx, fb.nblk[k]);
+  if (prm.free_pp) {
+    hipLaunchKernelGGL((fit_accum_kernel<Fit, Fit::NTH>), dim3(mx, fb.n), dim3(256), 0, s, fb, prm);
+    hipLaunchKernelGGL((fit_shared_reduce_kernel<Fit, Fit::NTH>), dim3(fb.n), dim3(64), 0, s, fb, rec);
+  } else {
+    hipLaunchKernelGGL((fit_accum_kernel<Fit, Fit::NTH - 2>), dim3(mx, fb.n), dim3(256), 0, s, fb, prm);
+    hipLaunchKernelGGL((fit_shared_reduce_kernel<Fit, Fit::NTH - 2>), dim3(fb.n), dim3(64), 0, s, fb, rec);
+  }
+}
+
+template <class Fit>
+void launch_fit_shared_solve(const FitGroups& fg, const FitParams& prm, hipStream_t s) {
+  if (prm.free_pp)
+    hipLaunchKernelGGL((fit_shared_solve_kernel<Fit, Fit::NTH>), dim3(fg.n), dim3(64), 0, s, fg);
+  else
+    hipLaunchKernelGGL((fit_shared_solve_kernel<Fit, Fit::NTH - 2>), dim3(fg.n), dim3(64), 0, s, fg);
 }
 
 }  // namespace pf

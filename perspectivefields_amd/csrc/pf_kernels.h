@@ -422,6 +422,23 @@ template <class Fit>
 void launch_fit_init(const FitBatch& fb, const FitParams& prm, hipStream_t s);
 template <class Fit>
 void launch_fit_iteration(const FitBatch& fb, const FitParams& prm, hipStream_t s);  // one accumulate + solve pair
+// The fit with intrinsics shared across the images of a camera group (include/pf_hip.h pf_fit_camera_shared): init and accumulate as above over
+// launch groups of FitBatch::MAX images, a per-image reduction into rec, then one solve per camera group.  Camera groups are consecutive images
+// anywhere in the batch, of any length; up to FitGroups::MAX of them per launch, state / rec / out are those of the whole batch
+struct FitGroups {
+  static constexpr int MAX = 128;
+  int n;
+  int start[MAX], size[MAX];  // first image and number of images of each camera group
+  double* state;              // [B][Fit::STATE]
+  const double* rec;          // [B][Fit::REC]: every image's summed record at its trial parameters
+  float* out;                 // [B][Fit::COLS]
+};
+template <class Fit>
+void launch_fit_shared_start(const FitGroups& fg, hipStream_t s);  // after launch_fit_init: the group's shared start
+template <class Fit>
+void launch_fit_shared_accum(const FitBatch& fb, const FitParams& prm, double* rec, hipStream_t s);  // accumulate + reduction; rec: of fb's first image
+template <class Fit>
+void launch_fit_shared_solve(const FitGroups& fg, const FitParams& prm, hipStream_t s);
 // camera parameters {roll, pitch (rad), focal_rel, cx_rel, cy_rel, xi} (device) -> up [2][H][W], latitude [H][W] degrees, NaN without a ray
 void launch_fields_usm(const float* cam6, int H, int W, float* up, float* lat, hipStream_t s);
 

@@ -64,6 +64,9 @@ _SIGNATURES = {
     "pf_fit_camera": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_int, _P, _P, _c.c_size_t, _P]),
     "pf_fit_camera_usm_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
     "pf_fit_camera_usm": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_int, _P, _P, _c.c_size_t, _P]),
+    "pf_fit_camera_shared_workspace_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _P, _c.c_int, _P]),
+    "pf_fit_camera_shared": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_int,
+                                        _P, _P, _c.c_size_t, _P]),
     "pf_fields_from_params_usm": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _P, _P, _P]),
     "pf_pano_crop": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     "pf_field_errors_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
