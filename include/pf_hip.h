@@ -418,6 +418,38 @@ int pf_pano_crop(int device, int n_pano, const void* const* h_pano, const int32_
                  const int32_t* h_pano_index /*[batch]*/, const float* d_cam7 /*[batch][7]*/, int H, int W,
                  void* d_img /*[batch][H][W][3], dtype*/, float* d_up /*[batch][2][H][W]*/, float* d_lat /*[batch][H][W]*/, void* stream);
 
+/* The image of one camera re-projected into another camera of the same centre, on the device: upright rectification (roll, or roll and
+ * pitch, removed), undistortion of a Unified Spherical Model view (xi -> 0), a change of focal length, principal point or output size, or
+ * any other camera of the same centre (reproject.hip).
+ * Per output, two cameras theta = {roll r, pitch p, yaw psi (RADIANS), rel_focal f, rel_cx cx, rel_cy cy, xi}: the source's row of d_cam_src7 and
+ * the destination's row of d_cam_dst7, DEVICE [batch][7] each.  Intrinsics, ray and rotation are pf_pano_crop's: F = f*H, Cx = (cx + 1/2)*W,
+ * Cy = (cy + 1/2)*H (of the camera's own image: H x W for the destination, Hs x Ws for the source), R = R_pitch(p) R_roll(r), camera -> world.
+ * Yaw is a turn about the world's vertical, Y(psi) = [[cos psi, 0, sin psi], [0, 1, 0], [-sin psi, 0, cos psi]], so that
+ * atan2(x', z') = atan2(x, z) + psi: pf_pano_crop's longitude.  For destination pixel (row, col):
+ *   1 ray       (a, b) = (col + 1/2, row + 1/2), x = (a - Cx_d)/F_d, y = (b - Cy_d)/F_d, X_d = pf_pano_crop's ray of (x, y, xi_d); disc < 0 (only for
+ *               xi_d > 1): the pixel has no ray and is invalid
+ *   2 source    X_s = M X_d, M = R_s^T Y(psi_d - psi_s) R_d, computed once per output on the device
+ *   3 visible   iff X_s.z > z_min(xi_s), z_min = -xi_s for xi_s <= 1 (0 for the pinhole camera), -1/xi_s for xi_s > 1: exactly the rays that the
+ *               ray formula's "+" root gives, so project o unproject is the identity on them
+ *   4 point     D = X_s.z + xi_s |X_s|, a_s = F_s X_s.x / D + Cx_s, b_s = F_s X_s.y / D + Cy_s; pixel-edge coordinates, a pixel centre at integer + 1/2
+ *   5 inside    valid iff visible and 0 <= a_s <= Ws and 0 <= b_s <= Hs
+ *   6 sample    bilinear at (u, v) = (a_s - 1/2, b_s - 1/2), the four tap indices clamped to [0, Ws - 1] x [0, Hs - 1]: the outer half-pixel rim
+ *               replicates the edge
+ *   7 value     PF_PANO_U8: the fp32 value rounded half up, clamped to [0, 255]; PF_PANO_F32: the value.  Invalid: `fill` (converted like a
+ *               value) in the image, 0 in the mask
+ * Every comparison is a positive one: NaN or infinite coordinates (non-finite parameters) make a pixel invalid, and no load is issued for it.
+ * No antialiasing and no mip levels: a strong minification aliases.
+ * h_src = HOST array of n_src DEVICE pointers, (Hs, Ws, 3) channel-interleaved, all of type `dtype` (PF_PANO_U8 | PF_PANO_F32); h_src_hw = HOST
+ * [n_src][2] (Hs, Ws), each >= 1; h_src_index = HOST [batch], the source of each output.  Every output is H x W (>= 1 each).
+ * d_img = DEVICE [batch][H][W][3] of `dtype` (required); d_valid = DEVICE [batch][H][W] uint8, 1 where valid, or NULL; d_map = DEVICE
+ * [batch][2][H][W] fp32, (a_s, b_s), NaN where not visible (finite where visible but outside the source), or NULL.
+ * Argument errors (NULL pointers, n_src < 1, a source size < 1, an index out of range, a bad dtype, H or W < 1, batch < 1) return PF_ERR_ARG
+ * before any device work.  One launch per 32 outputs on `stream`, no host synchronisation; stateless, no handle; deterministic, each output's
+ * bits independent of the batch it is in. */
+int pf_reproject(int device, int n_src, const void* const* h_src, const int32_t* h_src_hw /*[n_src][2]*/, int dtype /*PF_PANO_U8|PF_PANO_F32*/,
+                 int batch, const int32_t* h_src_index /*[batch]*/, const float* d_cam_src7 /*[batch][7]*/, const float* d_cam_dst7 /*[batch][7]*/,
+                 int H, int W, float fill, void* d_img, uint8_t* d_valid /*or NULL*/, float* d_map /*or NULL*/, void* stream);
+
 /* Predicted perspective fields against ground truth on the device: per-pixel errors, per-image statistics with an exact median, and
  * a running histogram for dataset statistics (field_err.hip).
  * Inputs per image: up_pred, up_gt [2][H][W] and lat_pred, lat_gt [H][W] degrees, fp32 (the layout of pred_gravity_original /

@@ -78,6 +78,16 @@ __device__ __forceinline__ bool usm_ray(float x, float y, float xi, float* X) {
   return true;
 }
 
+// the inverse: the normalised image point (x, y) of a ray X of any length, (X_x, X_y) / (X_z + xi |X|).  usm_ray's "+" root gives exactly the
+// rays with X_z > usm_z_min(xi) |X|; on those the denominator is positive and usm_project(usm_ray(x, y)) = (x, y)
+__device__ __forceinline__ void usm_project(const float* X, float xi, float* x, float* y) {
+  const float D = X[2] + xi * sqrtf(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
+  *x = X[0] / D;
+  *y = X[1] / D;
+}
+// lower bound (exclusive) of X_z of a unit ray that the camera sees: -xi for xi <= 1 (0 for the pinhole camera), -1 / xi beyond; NaN for a NaN xi
+__device__ __forceinline__ float usm_z_min(float xi) { return xi > 1.f ? -1.f / xi : 0.f - xi; }
+
 __device__ __forceinline__ void to_world(const float* R, const float* X, float* Xw) {
   Xw[0] = R[0] * X[0] + R[1] * X[1] + R[2] * X[2];
   Xw[1] = R[3] * X[0] + R[4] * X[1] + R[5] * X[2];

@@ -2146,6 +2146,52 @@ int pf_pano_crop(int device, int n_pano, const void* const* pano, const int32_t*
   return PF_OK;
 }
 
+int pf_reproject(int device, int n_src, const void* const* src, const int32_t* src_hw, int dtype, int B, const int32_t* src_index,
+                 const float* d_cam_src7, const float* d_cam_dst7, int H, int W, float fill, void* d_img, uint8_t* d_valid, float* d_map, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_reproject: " + m; return PF_ERR_ARG; };
+  if (n_src < 1 || !src || !src_hw) return bad("needs at least one source image (h_src, h_src_hw)");
+  if (dtype != PF_PANO_U8 && dtype != PF_PANO_F32) return bad(fmt("unknown dtype %d", dtype));
+  for (int k = 0; k < n_src; ++k) {
+    if (!src[k]) return bad(fmt("NULL pointer of source %d", k));
+    if (src_hw[2 * k] < 1 || src_hw[2 * k + 1] < 1) return bad(fmt("source %d is %d x %d, smaller than 1 x 1", k, src_hw[2 * k], src_hw[2 * k + 1]));
+  }
+  if (B < 1 || !src_index || !d_cam_src7 || !d_cam_dst7 || !d_img) return bad("batch >= 1, h_src_index, d_cam_src7, d_cam_dst7 and d_img are required");
+  if (H < 1 || W < 1) return bad(fmt("output size %d x %d", H, W));
+  for (int i = 0; i < B; ++i)
+    if (src_index[i] < 0 || src_index[i] >= n_src) return bad(fmt("output %d: source index %d of %d", i, src_index[i], n_src));
+  const int tpr = 16;  // a 64 x 16 pixel tile
+  const long tiles_x = (W + 4 * tpr - 1) / (4 * tpr), tiles_y = (H + 256 / tpr - 1) / (256 / tpr);
+  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("output size %d x %d too large", H, W));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  const size_t esz = dtype == PF_PANO_U8 ? 1 : 4, npx = (size_t)H * W;
+  const uintptr_t align = (reinterpret_cast<uintptr_t>(d_img) & (dtype == PF_PANO_U8 ? 3 : 15)) | (reinterpret_cast<uintptr_t>(d_valid) & 3) |
+                          (reinterpret_cast<uintptr_t>(d_map) & 15);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i0 = 0; i0 < B; i0 += ReprojBatch::MAX) {
+    ReprojBatch rb;
+    rb.n = std::min(B - i0, (int)ReprojBatch::MAX);
+    rb.H = H; rb.W = W;
+    rb.tpr = tpr; rb.tiles_x = (int)tiles_x; rb.tiles_y = (int)tiles_y;
+    rb.vec = (W % 4 == 0 && align == 0) ? 1 : 0;
+    rb.fill = fill;
+    for (int k = 0; k < rb.n; ++k) {
+      const int p = src_index[i0 + k];
+      rb.src[k] = src[p];
+      rb.Hs[k] = src_hw[2 * p]; rb.Ws[k] = src_hw[2 * p + 1];
+    }
+    rb.cam_src = d_cam_src7 + (size_t)i0 * 7;
+    rb.cam_dst = d_cam_dst7 + (size_t)i0 * 7;
+    rb.img = static_cast<char*>(d_img) + (size_t)i0 * npx * 3 * esz;
+    rb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
+    rb.map = d_map ? d_map + (size_t)i0 * 2 * npx : nullptr;
+    launch_reproject(rb, dtype, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_reproject: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
 // workspace of pf_fit_camera / pf_fit_camera_usm: per-image LM state, then every image's partial records, each region 256-byte aligned.
 // The two fits differ in their state, record, start and output row sizes and in their kernels only.
 struct FitKind {

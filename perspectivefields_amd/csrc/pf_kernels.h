@@ -458,6 +458,24 @@ struct PanoBatch {
 };
 void launch_pano_crop(const PanoBatch& pb, int dtype, hipStream_t s);
 
+// image of one camera -> image of another camera of the same centre (reproject.hip, include/pf_hip.h pf_reproject): up to
+// ReprojBatch::MAX outputs of one size per launch, per-output source pointers and sizes in the kernel arguments
+struct ReprojBatch {
+  static constexpr int MAX = 32;
+  int n, H, W;
+  int tpr, tiles_x, tiles_y;  // as PanoBatch: the tile is 4 tpr x 256 / tpr pixels
+  int vec;                    // 1: W % 4 == 0 and aligned outputs (image as PanoBatch, mask 4 bytes, map 16 bytes): vector stores
+  float fill;                 // value of a pixel that sees nothing of its source
+  const void* src[MAX];       // (Hs, Ws, 3) uint8 or fp32
+  int Hs[MAX], Ws[MAX];
+  const float* cam_src;  // [n][7]: roll, pitch, yaw (radians), rel_focal, rel_cx, rel_cy, xi
+  const float* cam_dst;  // [n][7]
+  void* img;             // [n][H][W][3], the sources' type
+  uint8_t* valid;        // NULL or [n][H][W]
+  float* map;            // NULL or [n][2][H][W]: (a_s, b_s), NaN where not visible
+};
+void launch_reproject(const ReprojBatch& rb, int dtype, hipStream_t s);
+
 // predicted fields against ground truth (field_err.hip, include/pf_hip.h pf_field_errors): up to FerrBatch::MAX images per launch,
 // per-image sizes and pointers in the kernel arguments
 constexpr int FERR_REC = 10;         // doubles of one accumulate block's partial record

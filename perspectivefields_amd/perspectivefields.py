@@ -19,6 +19,7 @@ import ctypes
 import operator
 import os
 from collections import OrderedDict
+from collections.abc import Mapping
 from typing import Dict, List, Optional, Union
 
 import numpy as np
@@ -496,6 +497,42 @@ class PerspectiveFields(nn.Module):
         plist = [preds] if single else list(preds)
         ups, lats = [p["pred_gravity_original"] for p in plist], [p["pred_latitude_original"] for p in plist]
         return field_errors(ups[0], lats[0], up_gt, lat_gt, **kw) if single else field_errors(ups, lats, up_gt, lat_gt, **kw)
+
+    def rectify(self, images, preds, *, level="roll", undistort=True, rel_focal=None, height=None, width=None, **kw):
+        """The images warped with their recovered cameras, on the GPU (see reproject_image for `images`, the other options --
+        src_index, fill, return_valid, return_map -- and what is returned).  preds: one result dict, or a list of them, of inference*
+        (a ParamNet model) or of fit_camera; the source camera is pred_roll, pred_pitch, pred_rel_focal, pred_rel_cx, pred_rel_cy and
+        pred_xi (absent keys count as 0), one per image (or per src_index entry).
+        level: "roll" -- the destination camera has roll 0 and the source's pitch (an upright view); "full" -- roll 0 and pitch 0 (the
+        horizon through the centre); "none" -- both kept.  The destination is always centred (rel_cx = rel_cy = 0).  undistort=True
+        gives it xi = 0 (a pinhole view), False keeps the source's xi.  rel_focal: its focal length (in heights of the output), default the
+        source's.  height, width: the output size, default the images'.
+        The perspective fields of the rectified view are `fields_from_params` of the destination camera (roll, pitch, rel_focal, 0, 0, xi
+        as stated here); they need no network."""
+        if level not in ("roll", "full", "none"):
+            raise ValueError("level must be 'roll', 'full' or 'none'")
+        if "mode" in kw:
+            raise ValueError("rectify takes the angles of its preds, which are degrees: no mode")
+        plist = [preds] if isinstance(preds, dict) else list(preds)
+        if not plist:
+            raise ValueError("rectify needs at least one result dict")
+        for p in plist:
+            if any(k not in p for k in ("pred_roll", "pred_pitch", "pred_rel_focal")):
+                raise PfError("rectify needs camera parameters (pred_roll, pred_pitch, pred_rel_focal) and this result has none: a PersNet "
+                              "model predicts fields only; pass the result of fit_camera(preds) instead")
+
+        def column(key):  # one value per result, on the device where the results hold tensors
+            vals = [p.get(key, 0.0) for p in plist]
+            tens = [v for v in vals if torch.is_tensor(v)]
+            if not tens:
+                return np.asarray(vals, dtype=np.float64)
+            return torch.stack([v.reshape(()).to(device=tens[0].device, dtype=torch.float64) if torch.is_tensor(v)
+                                else torch.tensor(float(v), dtype=torch.float64, device=tens[0].device) for v in vals])
+
+        src = {k: column("pred_" + k) for k in ("roll", "pitch", "rel_focal", "rel_cx", "rel_cy", "xi")}
+        dst = dict(roll=src["roll"] if level == "none" else 0.0, pitch=0.0 if level == "full" else src["pitch"],
+                   rel_focal=src["rel_focal"] if rel_focal is None else rel_focal, xi=0.0 if undistort else src["xi"])
+        return reproject_image(images, src, dst, height=height, width=width, mode="deg", **kw)
 
     def forward(self, batched_inputs) -> List[dict]:
         """batched_inputs: list of {"image": (3,320,320) float BGR 0..255, "height", "width"} (reference :223-272)."""
@@ -1145,3 +1182,117 @@ def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0
         _check(lib.pf_pano_crop(dev.index, n, p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, cam.data_ptr(), H, W, img.data_ptr(),
                                 up.data_ptr() if fields else None, lat.data_ptr() if fields else None, _stream_ptr()), None, "pf_pano_crop")
     return img, up, lat
+
+
+_CAM_KEYS = ("roll", "pitch", "yaw", "rel_focal", "rel_cx", "rel_cy", "xi")   # the row order of pf_reproject's d_cam_src7 / d_cam_dst7
+_CAM_REQUIRED = ("roll", "pitch", "rel_focal")
+
+
+def _camera_params(what, cam):
+    """a camera dict -> its seven values as tensors in the order of _CAM_KEYS, checked where they are (nothing moves to the device yet)"""
+    if not isinstance(cam, Mapping):
+        raise TypeError(f"reproject_image: {what} must be a dict of camera parameters; got {type(cam).__name__}")
+    unknown = [k for k in cam if k not in _CAM_KEYS]
+    missing = [k for k in _CAM_REQUIRED if k not in cam]
+    if unknown or missing:
+        raise ValueError(f"reproject_image: {what} needs {_CAM_REQUIRED} and may hold {_CAM_KEYS[2:3] + _CAM_KEYS[4:]}; unknown {unknown}, missing {missing}")
+    ts = []
+    for k in _CAM_KEYS:
+        v = cam.get(k, 0.0)
+        t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float64))
+        if t.dim() > 1:
+            raise ValueError(f"{what}[{k!r}] must be a number or a 1-d sequence; got shape {tuple(t.shape)}")
+        ts.append(t)
+    return ts
+
+
+def reproject_image(images, src, dst, *, height=None, width=None, src_index=None, mode="deg", fill=0, return_valid=False, return_map=False):
+    """Images of one camera -> images of another camera of the same centre on the GPU: upright rectification (destination roll 0, or roll
+    and pitch 0), undistortion of a Unified Spherical Model view (destination xi = 0), another focal length, principal point or output
+    size, or any other view of the same centre.  Model: include/pf_hip.h pf_reproject; the cameras are those of
+    `crop_panorama` and `fields_from_params`, so the perspective fields of the result are `fields_from_params` of `dst`.
+
+    images: a CUDA tensor (Hs, Ws, 3) or (B, Hs, Ws, 3), uint8 or float32, or a list of (Hs, Ws, 3) tensors of one dtype and one device,
+    whose sizes may differ.  src, dst: dicts with `roll`, `pitch`, `rel_focal` (required) and `yaw`, `rel_cx`, `rel_cy`, `xi` (default 0);
+    angles in degrees unless mode="rad"; each value a number, a 0-d tensor or a 1-d sequence / tensor, broadcast to the batch size B;
+    device tensors stay on the device.  src describes the camera that took the image, dst the camera to render.
+    B and the source of each output: with src_index (B integers into the images) B = len(src_index); otherwise one output per image, or,
+    for a single image, as many as the parameters broadcast to.  height, width: the size of every output; default: the size of the
+    sources (a ValueError when they differ).  fill: the value of the pixels that see nothing of their source (no ray, behind the
+    source camera, outside its image).
+    Returns the images (B, H, W, 3) in the sources' dtype; with return_valid / return_map a tuple that adds the mask (B, H, W) bool and /
+    or the map (B, 2, H, W) float32 of source coordinates (a_s, b_s) in pixel-edge units (NaN where the source camera does not see the ray).
+    Bilinear sampling without antialiasing or mip levels: a strong minification aliases.  GPU only: CPU images raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    batched = torch.is_tensor(images) and images.dim() == 4   # (B, Hs, Ws, 3): only as one tensor, not inside a list
+    srcs = [images] if torch.is_tensor(images) else list(images)
+    if not srcs or (batched and images.shape[0] < 1):
+        raise ValueError("reproject_image needs at least one image")
+    if not all(torch.is_tensor(p) for p in srcs):
+        raise TypeError("reproject_image takes torch tensors as images")
+    if not all(p.is_cuda for p in srcs):
+        raise PfError("reproject_image runs on the GPU only (no CPU path)")
+    for p in srcs:
+        if p.dim() != (4 if batched else 3) or p.shape[-1] != 3 or p.shape[-2] < 1 or p.shape[-3] < 1:
+            raise ValueError(f"an image must be (Hs, Ws, 3) with Hs, Ws >= 1, or a tensor (B, Hs, Ws, 3); got {tuple(p.shape)}")
+        if p.dtype not in _PANO_DTYPES:
+            raise ValueError(f"images must be uint8 or float32; got {p.dtype}")
+    if len({p.dtype for p in srcs}) != 1 or len({p.device for p in srcs}) != 1:
+        raise ValueError("reproject_image: all images must have one dtype and one device")
+    n = int(srcs[0].shape[0]) if batched else len(srcs)
+    sizes = [(int(srcs[0].shape[1]), int(srcs[0].shape[2]))] * n if batched else [(int(p.shape[0]), int(p.shape[1])) for p in srcs]
+    if height is None or width is None:
+        if len(set(sizes)) != 1:
+            raise ValueError("reproject_image: the images differ in size; give height and width")
+    H = sizes[0][0] if height is None else int(height)
+    W = sizes[0][1] if width is None else int(width)
+    if H < 1 or W < 1:
+        raise ValueError(f"output size must be at least 1 x 1; got {H} x {W}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    fill = float(fill)
+    ts = _camera_params("src", src) + _camera_params("dst", dst)
+    try:
+        shape = torch.broadcast_shapes(*[tuple(t.shape) for t in ts])
+    except RuntimeError as e:
+        raise ValueError(f"reproject_image: camera parameters do not broadcast: {e}") from None
+    Bp = int(shape[0]) if shape else 1
+    if src_index is not None:
+        idx = [operator.index(i) for i in (src_index.tolist() if torch.is_tensor(src_index) else src_index)]
+        if any(i < 0 or i >= n for i in idx):
+            raise ValueError(f"src_index entries must be in [0, {n})")
+    else:
+        idx = list(range(n)) if n > 1 else [0] * Bp
+    B = len(idx)
+    if B < 1:
+        raise ValueError("reproject_image needs at least one output")
+    if Bp not in (1, B):
+        raise ValueError(f"reproject_image: camera parameters of length {Bp} for {B} outputs")
+    dev = srcs[0].device
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    ts = [t.to(device=dev, dtype=torch.float64) for t in ts]   # as crop_panorama: degrees -> radians in fp64, then fp32
+    if mode == "deg":
+        for k in (0, 1, 2, 7, 8, 9):
+            ts[k] = torch.deg2rad(ts[k])
+    cam_s = torch.stack([t.expand(B) for t in ts[:7]], 1).to(torch.float32).contiguous()
+    cam_d = torch.stack([t.expand(B) for t in ts[7:]], 1).to(torch.float32).contiguous()
+    if batched:
+        whole = srcs[0].contiguous()
+        srcs = [whole[i] for i in range(n)]
+    else:
+        srcs = [p.contiguous() for p in srcs]
+    img = torch.empty((B, H, W, 3), dtype=srcs[0].dtype, device=dev)
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_valid else None
+    cmap = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if return_map else None
+    p_src = (ctypes.c_void_p * n)(*[p.data_ptr() for p in srcs])
+    hw = (ctypes.c_int32 * (2 * n))(*[s for hw_ in sizes for s in hw_])
+    c_idx = (ctypes.c_int32 * B)(*idx)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_reproject(dev.index, n, p_src, hw, _PANO_DTYPES[srcs[0].dtype], B, c_idx, cam_s.data_ptr(), cam_d.data_ptr(), H, W, fill,
+                                img.data_ptr(), valid.data_ptr() if return_valid else None, cmap.data_ptr() if return_map else None, _stream_ptr()),
+               None, "pf_reproject")
+    out = (img,) + ((valid.view(torch.bool),) if return_valid else ()) + ((cmap,) if return_map else ())
+    return out[0] if len(out) == 1 else out
