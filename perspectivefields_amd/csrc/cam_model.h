@@ -88,6 +88,19 @@ __device__ __forceinline__ void usm_project(const float* X, float xi, float* x, 
 // lower bound (exclusive) of X_z of a unit ray that the camera sees: -xi for xi <= 1 (0 for the pinhole camera), -1 / xi beyond; NaN for a NaN xi
 __device__ __forceinline__ float usm_z_min(float xi) { return xi > 1.f ? -1.f / xi : 0.f - xi; }
 
+// camera -> world, R = R_pitch(p) R_roll(r), row major, from the sines and cosines of roll and pitch
+__device__ __forceinline__ void cam_rotation(float sr, float cr, float sp, float cp, float* R) {
+  R[0] = cr; R[1] = -sr; R[2] = 0.f;
+  R[3] = cp * sr; R[4] = cp * cr; R[5] = -sp;
+  R[6] = sp * sr; R[7] = sp * cr; R[8] = cp;
+}
+__device__ __forceinline__ void cam_rotation(float roll, float pitch, float* R) {
+  float sr, cr, sp, cp;
+  sincosf(roll, &sr, &cr);
+  sincosf(pitch, &sp, &cp);
+  cam_rotation(sr, cr, sp, cp, R);
+}
+
 __device__ __forceinline__ void to_world(const float* R, const float* X, float* Xw) {
   Xw[0] = R[0] * X[0] + R[1] * X[1] + R[2] * X[2];
   Xw[1] = R[3] * X[0] + R[4] * X[1] + R[5] * X[2];

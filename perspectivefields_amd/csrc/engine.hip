@@ -2091,374 +2091,6 @@ int pf_postprocess_batch(pf_handle h, int B, const float* pg, const float* pl, c
   return PF_OK;
 }
 
-int pf_fields_from_params(int device, const float* d_cam5, int H, int W, float* d_up, float* d_lat, void* stream) {
-  std::string err;
-  int rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  if (!d_cam5 || !d_up || !d_lat || H <= 0 || W <= 0) { g_create_error = "pf_fields_from_params: bad argument"; return PF_ERR_ARG; }
-  launch_fields_from_params(d_cam5, H, W, d_up, d_lat, static_cast<hipStream_t>(stream));
-  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_fields_from_params: kernel launch failed"; return PF_ERR_DEVICE; }
-  return PF_OK;
-}
-
-int pf_pano_crop(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
-                 const float* d_cam7, int H, int W, void* d_img, float* d_up, float* d_lat, void* stream) {
-  auto bad = [](const std::string& m) { g_create_error = "pf_pano_crop: " + m; return PF_ERR_ARG; };
-  if (n_pano < 1 || !pano || !pano_hw) return bad("needs at least one panorama (h_pano, h_pano_hw)");
-  if (dtype != PF_PANO_U8 && dtype != PF_PANO_F32) return bad(fmt("unknown dtype %d", dtype));
-  for (int k = 0; k < n_pano; ++k) {
-    if (!pano[k]) return bad(fmt("NULL pointer of panorama %d", k));
-    if (pano_hw[2 * k] < 2 || pano_hw[2 * k + 1] < 2) return bad(fmt("panorama %d is %d x %d, smaller than 2 x 2", k, pano_hw[2 * k], pano_hw[2 * k + 1]));
-  }
-  if (B < 1 || !pano_index || !d_cam7 || !d_img) return bad("batch >= 1, h_pano_index, d_cam7 and d_img are required");
-  if (H < 1 || W < 1) return bad(fmt("output size %d x %d", H, W));
-  if (!d_up != !d_lat) return bad("d_up and d_lat are both given or both NULL");
-  for (int i = 0; i < B; ++i)
-    if (pano_index[i] < 0 || pano_index[i] >= n_pano) return bad(fmt("crop %d: panorama index %d of %d", i, pano_index[i], n_pano));
-  const int tpr = 16;  // a 64 x 16 pixel tile
-  const long tiles_x = (W + 4 * tpr - 1) / (4 * tpr), tiles_y = (H + 256 / tpr - 1) / (256 / tpr);
-  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("output size %d x %d too large", H, W));
-  std::string err;
-  const int rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  const size_t esz = dtype == PF_PANO_U8 ? 1 : 4, npx = (size_t)H * W;
-  const uintptr_t align = (reinterpret_cast<uintptr_t>(d_img) & (dtype == PF_PANO_U8 ? 3 : 15)) | (reinterpret_cast<uintptr_t>(d_up) & 15) |
-                          (reinterpret_cast<uintptr_t>(d_lat) & 15);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int i0 = 0; i0 < B; i0 += PanoBatch::MAX) {
-    PanoBatch pb;
-    pb.n = std::min(B - i0, (int)PanoBatch::MAX);
-    pb.H = H; pb.W = W;
-    pb.tpr = tpr; pb.tiles_x = (int)tiles_x; pb.tiles_y = (int)tiles_y;
-    pb.vec = (W % 4 == 0 && align == 0) ? 1 : 0;
-    for (int k = 0; k < pb.n; ++k) {
-      const int p = pano_index[i0 + k];
-      pb.pano[k] = pano[p];
-      pb.Hp[k] = pano_hw[2 * p]; pb.Wp[k] = pano_hw[2 * p + 1];
-    }
-    pb.cam = d_cam7 + (size_t)i0 * 7;
-    pb.img = static_cast<char*>(d_img) + (size_t)i0 * npx * 3 * esz;
-    pb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
-    pb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
-    launch_pano_crop(pb, dtype, s);
-  }
-  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_pano_crop: kernel launch failed"; return PF_ERR_DEVICE; }
-  return PF_OK;
-}
-
-int pf_reproject(int device, int n_src, const void* const* src, const int32_t* src_hw, int dtype, int B, const int32_t* src_index,
-                 const float* d_cam_src7, const float* d_cam_dst7, int H, int W, float fill, void* d_img, uint8_t* d_valid, float* d_map, void* stream) {
-  auto bad = [](const std::string& m) { g_create_error = "pf_reproject: " + m; return PF_ERR_ARG; };
-  if (n_src < 1 || !src || !src_hw) return bad("needs at least one source image (h_src, h_src_hw)");
-  if (dtype != PF_PANO_U8 && dtype != PF_PANO_F32) return bad(fmt("unknown dtype %d", dtype));
-  for (int k = 0; k < n_src; ++k) {
-    if (!src[k]) return bad(fmt("NULL pointer of source %d", k));
-    if (src_hw[2 * k] < 1 || src_hw[2 * k + 1] < 1) return bad(fmt("source %d is %d x %d, smaller than 1 x 1", k, src_hw[2 * k], src_hw[2 * k + 1]));
-  }
-  if (B < 1 || !src_index || !d_cam_src7 || !d_cam_dst7 || !d_img) return bad("batch >= 1, h_src_index, d_cam_src7, d_cam_dst7 and d_img are required");
-  if (H < 1 || W < 1) return bad(fmt("output size %d x %d", H, W));
-  for (int i = 0; i < B; ++i)
-    if (src_index[i] < 0 || src_index[i] >= n_src) return bad(fmt("output %d: source index %d of %d", i, src_index[i], n_src));
-  const int tpr = 16;  // a 64 x 16 pixel tile
-  const long tiles_x = (W + 4 * tpr - 1) / (4 * tpr), tiles_y = (H + 256 / tpr - 1) / (256 / tpr);
-  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("output size %d x %d too large", H, W));
-  std::string err;
-  const int rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  const size_t esz = dtype == PF_PANO_U8 ? 1 : 4, npx = (size_t)H * W;
-  const uintptr_t align = (reinterpret_cast<uintptr_t>(d_img) & (dtype == PF_PANO_U8 ? 3 : 15)) | (reinterpret_cast<uintptr_t>(d_valid) & 3) |
-                          (reinterpret_cast<uintptr_t>(d_map) & 15);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int i0 = 0; i0 < B; i0 += ReprojBatch::MAX) {
-    ReprojBatch rb;
-    rb.n = std::min(B - i0, (int)ReprojBatch::MAX);
-    rb.H = H; rb.W = W;
-    rb.tpr = tpr; rb.tiles_x = (int)tiles_x; rb.tiles_y = (int)tiles_y;
-    rb.vec = (W % 4 == 0 && align == 0) ? 1 : 0;
-    rb.fill = fill;
-    for (int k = 0; k < rb.n; ++k) {
-      const int p = src_index[i0 + k];
-      rb.src[k] = src[p];
-      rb.Hs[k] = src_hw[2 * p]; rb.Ws[k] = src_hw[2 * p + 1];
-    }
-    rb.cam_src = d_cam_src7 + (size_t)i0 * 7;
-    rb.cam_dst = d_cam_dst7 + (size_t)i0 * 7;
-    rb.img = static_cast<char*>(d_img) + (size_t)i0 * npx * 3 * esz;
-    rb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
-    rb.map = d_map ? d_map + (size_t)i0 * 2 * npx : nullptr;
-    launch_reproject(rb, dtype, s);
-  }
-  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_reproject: kernel launch failed"; return PF_ERR_DEVICE; }
-  return PF_OK;
-}
-
-// workspace of pf_fit_camera / pf_fit_camera_usm: per-image LM state, then every image's partial records, each region 256-byte aligned.
-// The two fits differ in their state, record, start and output row sizes and in their kernels only.
-struct FitKind {
-  const char* name;
-  int state, rec, ntheta, cols;
-  void (*init)(const FitBatch&, const FitParams&, hipStream_t);
-  void (*iteration)(const FitBatch&, const FitParams&, hipStream_t);
-};
-static const FitKind kFitPinhole{"pf_fit_camera", FIT_STATE, FIT_REC, 5, PF_FIT_COLS, launch_fit_init<PinholeFit>, launch_fit_iteration<PinholeFit>};
-static const FitKind kFitUsm{"pf_fit_camera_usm", USMFIT_STATE, USMFIT_REC, 6, PF_USMFIT_COLS, launch_fit_init<UsmFit>, launch_fit_iteration<UsmFit>};
-static size_t fit_state_bytes(const FitKind& fk, int B) { return ((size_t)B * fk.state * sizeof(double) + 255) & ~(size_t)255; }
-static size_t fit_part_bytes(const FitKind& fk, int H, int W) { return ((size_t)fit_blocks_per_image(H, W) * fk.rec * sizeof(double) + 255) & ~(size_t)255; }
-
-static size_t fit_workspace_bytes(const FitKind& fk, int B, const int32_t* hw) {
-  if (B <= 0 || !hw) return 0;
-  size_t n = 256 + fit_state_bytes(fk, B);  // + 256: alignment of the caller's pointer
-  for (int i = 0; i < B; ++i) {
-    if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) return 0;
-    n += fit_part_bytes(fk, hw[2 * i], hw[2 * i + 1]);
-  }
-  return n;
-}
-
-// the argument checks every camera fit makes before any device work; PF_OK or PF_ERR_ARG with g_create_error set
-static int fit_check_args(const char* name, int B, const int32_t* hw, const float* const* up, const float* const* lat, int free_pp, int loss,
-                          float huber_delta_deg, float w_up, float w_lat, int max_iter, const float* d_out) {
-  if (B <= 0 || !hw || !up || !lat || !d_out) { g_create_error = fmt("%s: bad argument", name); return PF_ERR_ARG; }
-  if ((free_pp != 0 && free_pp != 1) || (loss != PF_FIT_LOSS_L2 && loss != PF_FIT_LOSS_HUBER) || max_iter < 1 || max_iter > 1000) {
-    g_create_error = fmt("%s: bad option (free_pp %d, loss %d, max_iter %d)", name, free_pp, loss, max_iter);
-    return PF_ERR_ARG;
-  }
-  if (!(w_up >= 0.f && w_lat >= 0.f && std::isfinite(w_up) && std::isfinite(w_lat) && w_up + w_lat > 0.f) ||
-      (loss == PF_FIT_LOSS_HUBER && !(huber_delta_deg > 0.f && std::isfinite(huber_delta_deg)))) {
-    g_create_error = fmt("%s: weights must be finite, >= 0 and not both 0; huber_delta_deg must be finite and > 0", name);
-    return PF_ERR_ARG;
-  }
-  for (int i = 0; i < B; ++i) {
-    if (hw[2 * i] < 8 || hw[2 * i + 1] < 8) { g_create_error = fmt("%s: image %d is %d x %d, smaller than 8 x 8", name, i, hw[2 * i], hw[2 * i + 1]); return PF_ERR_ARG; }
-    if (!up[i] || !lat[i]) { g_create_error = fmt("%s: NULL field pointer of image %d", name, i); return PF_ERR_ARG; }
-  }
-  return PF_OK;
-}
-
-// the launch groups of a batch: FitBatch::MAX images each, their partial records laid out one after the other from `part`
-static std::vector<FitBatch> fit_batches(const FitKind& fk, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init,
-                                         double* state, char* part, float* d_out) {
-  std::vector<FitBatch> batches;
-  for (int i0 = 0; i0 < B; i0 += FitBatch::MAX) {
-    FitBatch fb;
-    fb.n = std::min(B - i0, (int)FitBatch::MAX);
-    for (int k = 0; k < fb.n; ++k) {
-      const int i = i0 + k, H = hw[2 * i], W = hw[2 * i + 1];
-      fb.H[k] = H; fb.W[k] = W; fb.nblk[k] = fit_blocks_per_image(H, W);
-      fb.up[k] = up[i]; fb.lat[k] = lat[i];
-      fb.part[k] = reinterpret_cast<double*>(part);
-      part += fit_part_bytes(fk, H, W);
-    }
-    fb.state = state + (size_t)i0 * fk.state;
-    fb.out = d_out + (size_t)i0 * fk.cols;
-    fb.init = d_init ? d_init + (size_t)i0 * fk.ntheta : nullptr;
-    batches.push_back(fb);
-  }
-  return batches;
-}
-
-static int fit_camera_run(const FitKind& fk, int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init,
-                          int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes,
-                          void* stream) {
-  int rc = fit_check_args(fk.name, B, hw, up, lat, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out);
-  if (rc != PF_OK) return rc;
-  const size_t need = fit_workspace_bytes(fk, B, hw);
-  if (!ws || ws_bytes < need) { g_create_error = fmt("%s: needs %zu workspace bytes, got %zu", fk.name, need, ws_bytes); return PF_ERR_WORKSPACE; }
-  std::string err;
-  rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat};
-  const std::vector<FitBatch> groups = fit_batches(fk, B, hw, up, lat, d_init, reinterpret_cast<double*>(base), base + fit_state_bytes(fk, B), d_out);
-  // no host synchronisation: every image stops on its own flag, the launches run out as no-ops
-  for (const FitBatch& fb : groups) fk.init(fb, prm, s);
-  for (int it = 0; it <= max_iter; ++it)
-    for (const FitBatch& fb : groups) fk.iteration(fb, prm, s);
-  if (hipGetLastError() != hipSuccess) { g_create_error = fmt("%s: kernel launch failed", fk.name); return PF_ERR_DEVICE; }
-  return PF_OK;
-}
-
-size_t pf_fit_camera_workspace_bytes(int B, const int32_t* hw) { return fit_workspace_bytes(kFitPinhole, B, hw); }
-
-int pf_fit_camera(int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int loss,
-                  float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes, void* stream) {
-  return fit_camera_run(kFitPinhole, device, B, hw, up, lat, d_init, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out, ws, ws_bytes, stream);
-}
-
-size_t pf_fit_camera_usm_workspace_bytes(int B, const int32_t* hw) { return fit_workspace_bytes(kFitUsm, B, hw); }
-
-int pf_fit_camera_usm(int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int loss,
-                      float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes, void* stream) {
-  return fit_camera_run(kFitUsm, device, B, hw, up, lat, d_init, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out, ws, ws_bytes, stream);
-}
-
-// pf_fit_camera_shared: the per-image fits' init and accumulate kernels over launch groups of FitBatch::MAX images, and per iteration one
-// reduction per image and one solve per camera group (fit_lm.h).  Workspace: that of the per-image fit, then the [B][rec] summed records.
-struct FitSharedKind {
-  const FitKind& fk;
-  void (*start)(const FitGroups&, hipStream_t);
-  void (*accum)(const FitBatch&, const FitParams&, double*, hipStream_t);
-  void (*solve)(const FitGroups&, const FitParams&, hipStream_t);
-};
-static const FitSharedKind kFitShared[2] = {
-    {kFitPinhole, launch_fit_shared_start<PinholeFit>, launch_fit_shared_accum<PinholeFit>, launch_fit_shared_solve<PinholeFit>},
-    {kFitUsm, launch_fit_shared_start<UsmFit>, launch_fit_shared_accum<UsmFit>, launch_fit_shared_solve<UsmFit>}};
-static size_t fit_rec_bytes(const FitKind& fk, int B) { return ((size_t)B * fk.rec * sizeof(double) + 255) & ~(size_t)255; }
-
-// group sizes: every entry >= 1, summing to B
-static bool fit_groups_ok(int B, int n_groups, const int32_t* gs, std::string* why) {
-  if (n_groups < 1 || !gs) { *why = fmt("bad group sizes (n_groups %d)", n_groups); return false; }
-  long sum = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    if (gs[g] < 1) { *why = fmt("bad group sizes (group %d has %d images)", g, gs[g]); return false; }
-    sum += gs[g];
-  }
-  if (sum != B) { *why = fmt("the group sizes sum to %ld, the batch is %d", sum, B); return false; }
-  return true;
-}
-
-size_t pf_fit_camera_shared_workspace_bytes(int model, int B, const int32_t* hw, int n_groups, const int32_t* group_sizes) {
-  std::string why;
-  if ((model != 0 && model != 1) || B <= 0 || !fit_groups_ok(B, n_groups, group_sizes, &why)) return 0;
-  const FitKind& fk = kFitShared[model].fk;
-  const size_t n = fit_workspace_bytes(fk, B, hw);
-  return n ? n + fit_rec_bytes(fk, B) : 0;
-}
-
-int pf_fit_camera_shared(int device, int model, int B, const int32_t* hw, const float* const* up, const float* const* lat, int n_groups,
-                         const int32_t* group_sizes, const float* d_init, int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter,
-                         float* d_out, void* ws, size_t ws_bytes, void* stream) {
-  const char* name = "pf_fit_camera_shared";
-  if (model != 0 && model != 1) { g_create_error = fmt("%s: model must be 0 (pinhole) or 1 (USM), got %d", name, model); return PF_ERR_ARG; }
-  int rc = fit_check_args(name, B, hw, up, lat, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out);
-  if (rc != PF_OK) return rc;
-  std::string why;
-  if (!fit_groups_ok(B, n_groups, group_sizes, &why)) { g_create_error = fmt("%s: %s", name, why.c_str()); return PF_ERR_ARG; }
-  for (int g = 0, i0 = 0; g < n_groups; i0 += group_sizes[g], ++g) {
-    for (int i = i0 + 1; i < i0 + group_sizes[g]; ++i) {
-      if (hw[2 * i] != hw[2 * i0] || hw[2 * i + 1] != hw[2 * i0 + 1]) {
-        g_create_error = fmt("%s: the images of a group must have one size (rel_focal is relative to the height): group %d has %d x %d and %d x %d", name, g,
-                             hw[2 * i0], hw[2 * i0 + 1], hw[2 * i], hw[2 * i + 1]);
-        return PF_ERR_ARG;
-      }
-    }
-  }
-  const FitSharedKind& sk = kFitShared[model];
-  const FitKind& fk = sk.fk;
-  const size_t need = fit_workspace_bytes(fk, B, hw) + fit_rec_bytes(fk, B);
-  if (!ws || ws_bytes < need) { g_create_error = fmt("%s: needs %zu workspace bytes, got %zu", name, need, ws_bytes); return PF_ERR_WORKSPACE; }
-  std::string err;
-  rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-  double* state = reinterpret_cast<double*>(base);
-  double* rec = reinterpret_cast<double*>(base + fit_state_bytes(fk, B));
-  char* part = base + fit_state_bytes(fk, B) + fit_rec_bytes(fk, B);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat};
-  const std::vector<FitBatch> batches = fit_batches(fk, B, hw, up, lat, d_init, state, part, d_out);
-  std::vector<FitGroups> groups;
-  for (int g0 = 0, i0 = 0; g0 < n_groups; g0 += FitGroups::MAX) {
-    FitGroups fg;
-    fg.n = std::min(n_groups - g0, (int)FitGroups::MAX);
-    for (int k = 0; k < fg.n; ++k) { fg.start[k] = i0; fg.size[k] = group_sizes[g0 + k]; i0 += group_sizes[g0 + k]; }
-    fg.state = state; fg.rec = rec; fg.out = d_out;
-    groups.push_back(fg);
-  }
-  // no host synchronisation: every group stops on its own flag, the launches run out as no-ops
-  for (const FitBatch& fb : batches) fk.init(fb, prm, s);
-  for (const FitGroups& fg : groups) sk.start(fg, s);
-  for (int it = 0; it <= max_iter; ++it) {
-    for (size_t k = 0; k < batches.size(); ++k) sk.accum(batches[k], prm, rec + k * FitBatch::MAX * fk.rec, s);
-    for (const FitGroups& fg : groups) sk.solve(fg, prm, s);
-  }
-  if (hipGetLastError() != hipSuccess) { g_create_error = fmt("%s: kernel launch failed", name); return PF_ERR_DEVICE; }
-  return PF_OK;
-}
-
-int pf_fields_from_params_usm(int device, const float* d_cam6, int H, int W, float* d_up, float* d_lat, void* stream) {
-  if (!d_cam6 || !d_up || !d_lat || H <= 0 || W <= 0) { g_create_error = "pf_fields_from_params_usm: bad argument"; return PF_ERR_ARG; }
-  std::string err;
-  const int rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  launch_fields_usm(d_cam6, H, W, d_up, d_lat, static_cast<hipStream_t>(stream));
-  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_fields_from_params_usm: kernel launch failed"; return PF_ERR_DEVICE; }
-  return PF_OK;
-}
-
-// workspace of pf_field_errors: per-image selection state, output rows (used when d_out is NULL), the level histograms of every image (one
-// region, zeroed per call), then per image the partial records and the two error maps (used unless the caller gives maps); 256-byte aligned
-static size_t ferr_align(size_t n) { return (n + 255) & ~(size_t)255; }
-static size_t ferr_hist_bytes() { return (size_t)3 * FERR_SEL * FERR_LEVEL_BINS * sizeof(unsigned); }
-static size_t ferr_part_bytes(int H, int W) { return ferr_align((size_t)ferr_blocks_per_image(H, W) * FERR_REC * sizeof(double)); }
-static size_t ferr_map_bytes(int H, int W) { return ferr_align((size_t)H * W * sizeof(float)); }
-static bool ferr_size_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1LL << 31); }
-
-size_t pf_field_errors_workspace_bytes(int B, const int32_t* hw) {
-  if (B <= 0 || !hw) return 0;
-  size_t n = 256 + ferr_align((size_t)B * sizeof(FerrState)) + ferr_align((size_t)B * PF_FERR_COLS * sizeof(double)) + (size_t)B * ferr_hist_bytes();
-  for (int i = 0; i < B; ++i) {
-    if (!ferr_size_ok(hw[2 * i], hw[2 * i + 1])) return 0;
-    n += ferr_part_bytes(hw[2 * i], hw[2 * i + 1]) + 2 * ferr_map_bytes(hw[2 * i], hw[2 * i + 1]);
-  }
-  return n;
-}
-
-int pf_field_errors(int device, int B, const int32_t* hw, const float* const* up_pred, const float* const* lat_pred, const float* const* up_gt,
-                    const float* const* lat_gt, float threshold_deg, double* d_out, float* const* err_up, float* const* err_lat, int64_t* d_hist,
-                    double* d_hist_sums, void* ws, size_t ws_bytes, void* stream) {
-  auto bad = [](const std::string& m) { g_create_error = "pf_field_errors: " + m; return PF_ERR_ARG; };
-  if (B <= 0 || !hw || !up_pred || !lat_pred || !up_gt || !lat_gt) return bad("batch >= 1, h_hw and the four field pointer arrays are required");
-  if (!(threshold_deg > 0.f && std::isfinite(threshold_deg))) return bad("threshold_deg must be finite and > 0");
-  if (!err_up != !err_lat) return bad("h_err_up and h_err_lat are both given or both NULL");
-  if (!d_hist != !d_hist_sums) return bad("d_hist and d_hist_sums are both given or both NULL");
-  for (int i = 0; i < B; ++i) {
-    if (!ferr_size_ok(hw[2 * i], hw[2 * i + 1])) return bad(fmt("image %d is %d x %d", i, hw[2 * i], hw[2 * i + 1]));
-    if (!up_pred[i] || !lat_pred[i] || !up_gt[i] || !lat_gt[i]) return bad(fmt("NULL field pointer of image %d", i));
-    if (err_up && (!err_up[i] || !err_lat[i])) return bad(fmt("NULL error-map pointer of image %d", i));
-  }
-  const size_t need = pf_field_errors_workspace_bytes(B, hw);
-  if (!ws || ws_bytes < need) { g_create_error = fmt("pf_field_errors: needs %zu workspace bytes, got %zu", need, ws_bytes); return PF_ERR_WORKSPACE; }
-  std::string err;
-  const int rc = check_device(device, &err);
-  if (rc != PF_OK) { g_create_error = err; return rc; }
-  char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-  FerrState* state = reinterpret_cast<FerrState*>(p);
-  p += ferr_align((size_t)B * sizeof(FerrState));
-  double* rows = d_out ? d_out : reinterpret_cast<double*>(p);
-  p += ferr_align((size_t)B * PF_FERR_COLS * sizeof(double));
-  char* hist = p;
-  p += (size_t)B * ferr_hist_bytes();
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(hist, 0, (size_t)B * ferr_hist_bytes(), s) != hipSuccess) { g_create_error = "pf_field_errors: hipMemsetAsync failed"; return PF_ERR_DEVICE; }
-  for (int i0 = 0; i0 < B; i0 += FerrBatch::MAX) {
-    FerrBatch fb;
-    fb.n = std::min(B - i0, (int)FerrBatch::MAX);
-    for (int k = 0; k < fb.n; ++k) {
-      const int i = i0 + k, H = hw[2 * i], W = hw[2 * i + 1];
-      fb.H[k] = H; fb.W[k] = W; fb.nblk[k] = ferr_blocks_per_image(H, W);
-      fb.up_pred[k] = up_pred[i]; fb.lat_pred[k] = lat_pred[i]; fb.up_gt[k] = up_gt[i]; fb.lat_gt[k] = lat_gt[i];
-      fb.part[k] = reinterpret_cast<double*>(p);
-      p += ferr_part_bytes(H, W);
-      fb.err_up[k] = err_up ? err_up[i] : reinterpret_cast<float*>(p);
-      fb.err_lat[k] = err_up ? err_lat[i] : reinterpret_cast<float*>(p + ferr_map_bytes(H, W));
-      p += 2 * ferr_map_bytes(H, W);
-      fb.hist[k] = reinterpret_cast<unsigned*>(hist + (size_t)i * ferr_hist_bytes());
-      const uintptr_t align = reinterpret_cast<uintptr_t>(up_pred[i]) | reinterpret_cast<uintptr_t>(lat_pred[i]) | reinterpret_cast<uintptr_t>(up_gt[i]) |
-                              reinterpret_cast<uintptr_t>(lat_gt[i]) | reinterpret_cast<uintptr_t>(fb.err_up[k]) | reinterpret_cast<uintptr_t>(fb.err_lat[k]);
-      fb.vec[k] = (((size_t)H * W) % 4 == 0 && (align & 15) == 0) ? 1 : 0;  // H * W % 4: the second up plane starts at up + H * W
-    }
-    fb.state = state + i0;
-    fb.out = rows + (size_t)i0 * PF_FERR_COLS;
-    fb.threshold = threshold_deg;
-    launch_field_errors(fb, s);
-    if (d_hist) launch_field_errors_hist(fb, reinterpret_cast<long long*>(d_hist), d_hist_sums, s);
-  }
-  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_field_errors: kernel launch failed"; return PF_ERR_DEVICE; }
-  return PF_OK;
-}
-
 int pf_profile_begin(pf_handle h, unsigned class_mask) {
   if (!h) return PF_ERR_ARG;
   h->prof.reset();

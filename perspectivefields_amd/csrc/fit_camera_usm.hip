@@ -231,10 +231,10 @@ __global__ __launch_bounds__(256) void fields_usm_kernel(const float* __restrict
   const long n = (long)H * W, nchunk = (n + 3) >> 2;
   const float roll = cam[0], pitch = cam[1], f = cam[2], rcx = cam[3], rcy = cam[4], xi = cam[5];
   const PinholeFields pin = pinhole_fields_setup(roll, pitch, f, rcx, rcy, H, W);
-  float sr, cr, sp, cp;
+  float sr, cr, sp, cp, R[9];
   sincosf(roll, &sr, &cr);
   sincosf(pitch, &sp, &cp);
-  const float R[9] = {cr, -sr, 0.f, cp * sr, cp * cr, -sp, sp * sr, sp * cr, cp};
+  cam_rotation(sr, cr, sp, cp, R);
   const float g[3] = {-R[3], -R[4], -R[5]};
   const float F = f * (float)H, invF = 1.f / F, Cx = (rcx + 0.5f) * (float)W, Cy = (rcy + 0.5f) * (float)H;
   const float sx = W > 1 ? (float)W / (float)(W - 1) : 0.f, sy = H > 1 ? (float)H / (float)(H - 1) : 0.f;

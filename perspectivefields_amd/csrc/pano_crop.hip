@@ -2,7 +2,7 @@
 // (include/pf_hip.h pf_pano_crop): the reference's PanoCam.get_image / crop_equi / crop_distortion and
 // get_up_general / get_lat_general (utils/panocam.py) as one batched gather.  VALU and memory bound, no MFMA, no atomics.
 //   pano_crop_kernel<T, LABELS>  grid (tiles per crop) x (crops of the group), 256 threads.  Each block owns a compact 2-D tile of
-//                                output pixels (PanoBatch::tpr threads x 4 pixels across, 256 / tpr rows; 64 x 16 as launched), so
+//                                output pixels (GatherDims::tpr threads x 4 pixels across, 256 / tpr rows; 64 x 16 as launched), so
 //                                its bilinear gathers stay in a small region of the panorama.  Lane 0 computes the crop's constants (R, g, F, Cx, Cy,
 //                                xi) into LDS once per block.  Every output value depends on its own crop's parameters and
 //                                panorama only: the same bits in any batch and on every run.
@@ -22,7 +22,7 @@
 
 #include "../../include/pf_hip.h"
 #include "cam_model.h"
-#include "pf_kernels.h"
+#include "gather.h"
 
 namespace pf {
 
@@ -37,32 +37,20 @@ struct CropConsts {
   PinholeFields pin;  // the xi == 0 labels
 };
 
-__device__ __forceinline__ float texel(const uint8_t* p, size_t i) { return (float)p[i]; }
-__device__ __forceinline__ float texel(const float* p, size_t i) { return p[i]; }
-
-// bilinear sample of channel-interleaved (Hp, Wp, 3) texels at (u, v); every index is forced into the panorama
+// bilinear sample of channel-interleaved (Hp, Wp, 3) texels at (u, v): columns wrap, rows clamp, every index is forced into the panorama
 template <typename T>
 __device__ __forceinline__ void sample(const T* __restrict__ pano, int Hp, int Wp, float u, float v, float* out) {
   const float uf = floorf(u), vf = floorf(v);
   const float fu = u - uf, fv = v - vf;
   int c0 = (int)uf;
-  if (c0 < 0) c0 += Wp;
-  if (c0 >= Wp) c0 -= Wp;
-  if ((unsigned)c0 >= (unsigned)Wp) c0 = 0;
+  c0 = c0 < 0 ? c0 + Wp : c0;
+  c0 = c0 >= Wp ? c0 - Wp : c0;
+  c0 = (unsigned)c0 >= (unsigned)Wp ? 0 : c0;
   const int c1 = c0 + 1 == Wp ? 0 : c0 + 1;
   const int r = (int)vf;
   const int r0 = min(max(r, 0), Hp - 1), r1 = min(max(r + 1, 0), Hp - 1);
-  const size_t i00 = ((size_t)r0 * Wp + c0) * 3, i01 = ((size_t)r0 * Wp + c1) * 3;
-  const size_t i10 = ((size_t)r1 * Wp + c0) * 3, i11 = ((size_t)r1 * Wp + c1) * 3;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float top = (1.f - fu) * texel(pano, i00 + k) + fu * texel(pano, i01 + k);
-    const float bot = (1.f - fu) * texel(pano, i10 + k) + fu * texel(pano, i11 + k);
-    out[k] = (1.f - fv) * top + fv * bot;
-  }
+  bilerp_rgb(pano, Wp, r0, r1, c0, c1, fu, fv, out);
 }
-
-__device__ __forceinline__ uint32_t round_u8(float v) { return (uint32_t)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f); }
 
 }  // namespace
 
@@ -70,14 +58,14 @@ template <typename T, bool LABELS>
 __global__ __launch_bounds__(256) void pano_crop_kernel(PanoBatch pb) {
   __shared__ CropConsts cc;
   const int crop = blockIdx.y;
-  const int H = pb.H, W = pb.W;
+  const int H = pb.d.H, W = pb.d.W;
   if (threadIdx.x == 0) {
     const float* cam = pb.cam + (size_t)crop * 7;
     const float roll = cam[0], pitch = cam[1], yaw = cam[2], f = cam[3], rcx = cam[4], rcy = cam[5], xi = cam[6];
-    float sr, cr, sp, cp;
+    float sr, cr, sp, cp, R[9];
     sincosf(roll, &sr, &cr);
     sincosf(pitch, &sp, &cp);
-    const float R[9] = {cr, -sr, 0.f, cp * sr, cp * cr, -sp, sp * sr, sp * cr, cp};
+    cam_rotation(sr, cr, sp, cp, R);
     for (int k = 0; k < 9; ++k) cc.R[k] = R[k];
     cc.g[0] = -R[3]; cc.g[1] = -R[4]; cc.g[2] = -R[5];
     cc.F = f * (float)H;
@@ -91,13 +79,13 @@ __global__ __launch_bounds__(256) void pano_crop_kernel(PanoBatch pb) {
     if (LABELS) cc.pin = pinhole_fields_setup(roll, pitch, f, rcx, rcy, H, W);
   }
   __syncthreads();
-  const int tpr = pb.tpr;  // threads per tile row; the tile is (4 tpr) x (256 / tpr) pixels
-  const int tile_x = blockIdx.x % pb.tiles_x, tile_y = blockIdx.x / pb.tiles_x;
+  const int tpr = pb.d.tpr;  // threads per tile row; the tile is (4 tpr) x (256 / tpr) pixels
+  const int tile_x = blockIdx.x % pb.d.tiles_x, tile_y = blockIdx.x / pb.d.tiles_x;
   const int row = tile_y * (256 / tpr) + threadIdx.x / tpr;
   const int col0 = tile_x * 4 * tpr + (threadIdx.x % tpr) * 4;
   if (row >= H || col0 >= W) return;
-  const T* __restrict__ pano = static_cast<const T*>(pb.pano[crop]);
-  const int Hp = pb.Hp[crop], Wp = pb.Wp[crop];
+  const T* __restrict__ pano = static_cast<const T*>(pb.src.p[crop]);
+  const int Hp = pb.src.H[crop], Wp = pb.src.W[crop];
   const float xi = cc.xi;
 
   float img[4][3], ux[4], uy[4], lat[4];
@@ -132,7 +120,7 @@ __global__ __launch_bounds__(256) void pano_crop_kernel(PanoBatch pb) {
 
   const size_t npx = (size_t)H * W, pix = (size_t)crop * npx + (size_t)row * W + col0;
   T* __restrict__ out = static_cast<T*>(pb.img) + pix * 3;
-  if (pb.vec) {  // W % 4 == 0 and aligned outputs: the 4 pixels are whole 16-byte label vectors and 12 / 48 image bytes
+  if (pb.d.vec) {  // W % 4 == 0 and aligned outputs: the 4 pixels are whole 16-byte label vectors and 12 / 48 image bytes
     if constexpr (sizeof(T) == 1) {
       uint32_t w[3] = {0u, 0u, 0u};
 #pragma unroll
@@ -140,10 +128,7 @@ __global__ __launch_bounds__(256) void pano_crop_kernel(PanoBatch pb) {
       uint32_t* o = reinterpret_cast<uint32_t*>(out);
       o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
     } else {
-      float4* o = reinterpret_cast<float4*>(out);
-      o[0] = make_float4(img[0][0], img[0][1], img[0][2], img[1][0]);
-      o[1] = make_float4(img[1][1], img[1][2], img[2][0], img[2][1]);
-      o[2] = make_float4(img[2][2], img[3][0], img[3][1], img[3][2]);
+      store_rgb4(out, img);
     }
     if (LABELS) {
       const size_t l = (size_t)crop * npx + (size_t)row * W + col0;
@@ -156,10 +141,7 @@ __global__ __launch_bounds__(256) void pano_crop_kernel(PanoBatch pb) {
     for (int k = 0; k < 4; ++k) {
       if (col0 + k >= W) break;
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        if constexpr (sizeof(T) == 1) out[3 * k + ch] = (uint8_t)round_u8(img[k][ch]);
-        else out[3 * k + ch] = img[k][ch];
-      }
+      for (int ch = 0; ch < 3; ++ch) store_px(out + 3 * k + ch, img[k][ch]);
       if (LABELS) {
         const size_t l = (size_t)crop * npx + (size_t)row * W + col0 + k;
         pb.up[l + (size_t)crop * npx] = ux[k];
@@ -171,7 +153,7 @@ __global__ __launch_bounds__(256) void pano_crop_kernel(PanoBatch pb) {
 }
 
 void launch_pano_crop(const PanoBatch& pb, int dtype, hipStream_t s) {
-  const dim3 grid((unsigned)(pb.tiles_x * pb.tiles_y), (unsigned)pb.n), block(256);
+  const dim3 grid((unsigned)(pb.d.tiles_x * pb.d.tiles_y), (unsigned)pb.d.n), block(256);
   const bool labels = pb.up != nullptr;
   if (dtype == PF_PANO_U8) {
     if (labels) hipLaunchKernelGGL((pano_crop_kernel<uint8_t, true>), grid, block, 0, s, pb);

@@ -442,15 +442,24 @@ void launch_fit_shared_solve(const FitGroups& fg, const FitParams& prm, hipStrea
 // camera parameters {roll, pitch (rad), focal_rel, cx_rel, cy_rel, xi} (device) -> up [2][H][W], latitude [H][W] degrees, NaN without a ray
 void launch_fields_usm(const float* cam6, int H, int W, float* up, float* lat, hipStream_t s);
 
-// equirectangular panorama -> camera views + ground-truth fields (pano_crop.hip, include/pf_hip.h pf_pano_crop): up to
-// PanoBatch::MAX crops of one output size per launch, per-crop panorama pointers and sizes in the kernel arguments
-struct PanoBatch {
+// The batched image gathers (gather.h): up to GatherSources::MAX outputs of one size per launch, grid (tiles per output) x (outputs), per-output source
+// pointers and sizes in the kernel arguments.  Both arguments begin with the launch's shape
+struct GatherDims {
+  int n, H, W;                // outputs of this launch, their size
+  int tpr, tiles_x, tiles_y;  // threads per tile row (the tile is 4 tpr x 256 / tpr pixels), tiles per output
+  int vec;                    // 1: W % 4 == 0 and every output aligned for the 4-pixel vector stores (uint8 image and mask 4 bytes, the rest 16)
+};
+struct GatherSources {  // of each output of the launch
   static constexpr int MAX = 32;
-  int n, H, W;
-  int tpr, tiles_x, tiles_y;  // threads per tile row (the tile is 4 tpr x 256 / tpr pixels), tiles per crop
-  int vec;                    // 1: W % 4 == 0 and 16-byte aligned outputs (4-byte for a uint8 image): vector stores
-  const void* pano[MAX];      // (Hp, Wp, 3) uint8 or fp32
-  int Hp[MAX], Wp[MAX];
+  const void* p[MAX];  // (H, W, 3) uint8 or fp32
+  int H[MAX], W[MAX];
+};
+
+// equirectangular panorama -> camera views + ground-truth fields (pano_crop.hip, include/pf_hip.h pf_pano_crop)
+struct PanoBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  GatherSources src;  // the panoramas (Hp, Wp, 3)
   const float* cam;  // [n][7]: roll, pitch, yaw (radians), rel_focal, rel_cx, rel_cy, xi
   void* img;         // [n][H][W][3], the panorama's type
   float* up;         // NULL (no labels) or [n][2][H][W]
@@ -458,16 +467,12 @@ struct PanoBatch {
 };
 void launch_pano_crop(const PanoBatch& pb, int dtype, hipStream_t s);
 
-// image of one camera -> image of another camera of the same centre (reproject.hip, include/pf_hip.h pf_reproject): up to
-// ReprojBatch::MAX outputs of one size per launch, per-output source pointers and sizes in the kernel arguments
+// image of one camera -> image of another camera of the same centre (reproject.hip, include/pf_hip.h pf_reproject)
 struct ReprojBatch {
-  static constexpr int MAX = 32;
-  int n, H, W;
-  int tpr, tiles_x, tiles_y;  // as PanoBatch: the tile is 4 tpr x 256 / tpr pixels
-  int vec;                    // 1: W % 4 == 0 and aligned outputs (image as PanoBatch, mask 4 bytes, map 16 bytes): vector stores
-  float fill;                 // value of a pixel that sees nothing of its source
-  const void* src[MAX];       // (Hs, Ws, 3) uint8 or fp32
-  int Hs[MAX], Ws[MAX];
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  float fill;         // value of a pixel that sees nothing of its source
+  GatherSources src;  // (Hs, Ws, 3)
   const float* cam_src;  // [n][7]: roll, pitch, yaw (radians), rel_focal, rel_cx, rel_cy, xi
   const float* cam_dst;  // [n][7]
   void* img;             // [n][H][W][3], the sources' type
@@ -475,6 +480,9 @@ struct ReprojBatch {
   float* map;            // NULL or [n][2][H][W]: (a_s, b_s), NaN where not visible
 };
 void launch_reproject(const ReprojBatch& rb, int dtype, hipStream_t s);
+// the kernel-argument layout both gathers were measured with
+static_assert(sizeof(PanoBatch) == 576 && offsetof(PanoBatch, src) == 32, "PanoBatch layout");
+static_assert(sizeof(ReprojBatch) == 584 && offsetof(ReprojBatch, fill) == 28 && offsetof(ReprojBatch, src) == 32, "ReprojBatch layout");
 
 // predicted fields against ground truth (field_err.hip, include/pf_hip.h pf_field_errors): up to FerrBatch::MAX images per launch,
 // per-image sizes and pointers in the kernel arguments

@@ -2,7 +2,7 @@
 // rectification, undistortion of a Unified Spherical Model view, a change of focal length, principal point or size, as one batched
 // gather.  VALU and memory bound, no MFMA, no atomics.
 //   reproject_kernel<T, EXTRAS>  grid (tiles per output) x (outputs of the group), 256 threads.  Each block owns a compact 2-D tile of
-//                                output pixels (ReprojBatch::tpr threads x 4 pixels across, 256 / tpr rows; 64 x 16 as launched), so its
+//                                output pixels (GatherDims::tpr threads x 4 pixels across, 256 / tpr rows; 64 x 16 as launched), so its
 //                                bilinear gathers stay in a small region of the source.  Lane 0 computes the output's constants (M, both
 //                                intrinsics, both xi, z_min) into LDS once per block.  EXTRAS: the mask and / or the map are written.
 //                                Every output value depends on its own two cameras and its own source only: the same bits in any
@@ -20,7 +20,7 @@
 
 #include "../../include/pf_hip.h"
 #include "cam_model.h"
-#include "pf_kernels.h"
+#include "gather.h"
 
 namespace pf {
 
@@ -32,19 +32,6 @@ struct ReprojConsts {
   float Fs, Cxs, Cys, xis, zmin;
 };
 
-// camera -> world, R_pitch(p) R_roll(r), row major (pano_crop.hip's)
-__device__ __forceinline__ void cam_rotation(float roll, float pitch, float* R) {
-  float sr, cr, sp, cp;
-  sincosf(roll, &sr, &cr);
-  sincosf(pitch, &sp, &cp);
-  R[0] = cr; R[1] = -sr; R[2] = 0.f;
-  R[3] = cp * sr; R[4] = cp * cr; R[5] = -sp;
-  R[6] = sp * sr; R[7] = sp * cr; R[8] = cp;
-}
-
-__device__ __forceinline__ float texel(const uint8_t* p, size_t i) { return (float)p[i]; }
-__device__ __forceinline__ float texel(const float* p, size_t i) { return p[i]; }
-
 // bilinear sample of channel-interleaved (Hs, Ws, 3) texels at (u, v), pixel centres at integers; the taps clamp into the image
 template <typename T>
 __device__ __forceinline__ void sample_clamped(const T* __restrict__ src, int Hs, int Ws, float u, float v, float* out) {
@@ -53,17 +40,8 @@ __device__ __forceinline__ void sample_clamped(const T* __restrict__ src, int Hs
   const int c = (int)uf, r = (int)vf;
   const int c0 = min(max(c, 0), Ws - 1), c1 = min(max(c + 1, 0), Ws - 1);
   const int r0 = min(max(r, 0), Hs - 1), r1 = min(max(r + 1, 0), Hs - 1);
-  const size_t i00 = ((size_t)r0 * Ws + c0) * 3, i01 = ((size_t)r0 * Ws + c1) * 3;
-  const size_t i10 = ((size_t)r1 * Ws + c0) * 3, i11 = ((size_t)r1 * Ws + c1) * 3;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float top = (1.f - fu) * texel(src, i00 + k) + fu * texel(src, i01 + k);
-    const float bot = (1.f - fu) * texel(src, i10 + k) + fu * texel(src, i11 + k);
-    out[k] = (1.f - fv) * top + fv * bot;
-  }
+  bilerp_rgb(src, Ws, r0, r1, c0, c1, fu, fv, out);
 }
-
-__device__ __forceinline__ uint32_t round_u8(float v) { return (uint32_t)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f); }
 
 }  // namespace
 
@@ -71,8 +49,8 @@ template <typename T, bool EXTRAS>
 __global__ __launch_bounds__(256) void reproject_kernel(ReprojBatch rb) {
   __shared__ ReprojConsts cc;
   const int o = blockIdx.y;
-  const int H = rb.H, W = rb.W;
-  const int Hs = rb.Hs[o], Ws = rb.Ws[o];
+  const int H = rb.d.H, W = rb.d.W;
+  const int Hs = rb.src.H[o], Ws = rb.src.W[o];
   if (threadIdx.x == 0) {
     const float* cs = rb.cam_src + (size_t)o * 7;
     const float* cd = rb.cam_dst + (size_t)o * 7;
@@ -99,12 +77,12 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojBatch rb) {
     cc.zmin = usm_z_min(cs[6]);
   }
   __syncthreads();
-  const int tpr = rb.tpr;  // threads per tile row; the tile is (4 tpr) x (256 / tpr) pixels
-  const int tile_x = blockIdx.x % rb.tiles_x, tile_y = blockIdx.x / rb.tiles_x;
+  const int tpr = rb.d.tpr;  // threads per tile row; the tile is (4 tpr) x (256 / tpr) pixels
+  const int tile_x = blockIdx.x % rb.d.tiles_x, tile_y = blockIdx.x / rb.d.tiles_x;
   const int row = tile_y * (256 / tpr) + threadIdx.x / tpr;
   const int col0 = tile_x * 4 * tpr + (threadIdx.x % tpr) * 4;
   if (row >= H || col0 >= W) return;
-  const T* __restrict__ src = static_cast<const T*>(rb.src[o]);
+  const T* __restrict__ src = static_cast<const T*>(rb.src.p[o]);
   const float fill = rb.fill, wmax = (float)Ws, hmax = (float)Hs;
 
   float img[4][3], ma[4], mb[4];
@@ -134,7 +112,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojBatch rb) {
 
   const size_t npx = (size_t)H * W, pix = (size_t)o * npx + (size_t)row * W + col0;
   T* __restrict__ out = static_cast<T*>(rb.img) + pix * 3;
-  if (rb.vec) {  // W % 4 == 0 and aligned outputs: 12 / 48 image bytes, 4 mask bytes and two 16-byte map vectors
+  if (rb.d.vec) {  // W % 4 == 0 and aligned outputs: 12 / 48 image bytes, 4 mask bytes and two 16-byte map vectors
     if constexpr (sizeof(T) == 1) {
       uint32_t w[3] = {0u, 0u, 0u};
 #pragma unroll
@@ -142,10 +120,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojBatch rb) {
       uint32_t* p = reinterpret_cast<uint32_t*>(out);
       p[0] = w[0]; p[1] = w[1]; p[2] = w[2];
     } else {
-      float4* p = reinterpret_cast<float4*>(out);
-      p[0] = make_float4(img[0][0], img[0][1], img[0][2], img[1][0]);
-      p[1] = make_float4(img[1][1], img[1][2], img[2][0], img[2][1]);
-      p[2] = make_float4(img[2][2], img[3][0], img[3][1], img[3][2]);
+      store_rgb4(out, img);
     }
     if (EXTRAS) {
       if (rb.valid) *reinterpret_cast<uint32_t*>(rb.valid + pix) = ok[0] | ok[1] << 8 | ok[2] << 16 | ok[3] << 24;
@@ -160,10 +135,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojBatch rb) {
     for (int k = 0; k < 4; ++k) {
       if (col0 + k >= W) break;
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        if constexpr (sizeof(T) == 1) out[3 * k + ch] = (uint8_t)round_u8(img[k][ch]);
-        else out[3 * k + ch] = img[k][ch];
-      }
+      for (int ch = 0; ch < 3; ++ch) store_px(out + 3 * k + ch, img[k][ch]);
       if (EXTRAS) {
         if (rb.valid) rb.valid[pix + k] = (uint8_t)ok[k];
         if (rb.map) {
@@ -176,7 +148,7 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojBatch rb) {
 }
 
 void launch_reproject(const ReprojBatch& rb, int dtype, hipStream_t s) {
-  const dim3 grid((unsigned)(rb.tiles_x * rb.tiles_y), (unsigned)rb.n), block(256);
+  const dim3 grid((unsigned)(rb.d.tiles_x * rb.d.tiles_y), (unsigned)rb.d.n), block(256);
   const bool extras = rb.valid != nullptr || rb.map != nullptr;
   if (dtype == PF_PANO_U8) {
     if (extras) hipLaunchKernelGGL((reproject_kernel<uint8_t, true>), grid, block, 0, s, rb);

@@ -1101,6 +1101,52 @@ PANO_U8, PANO_F32 = 0, 1
 _PANO_DTYPES = {torch.uint8: PANO_U8, torch.float32: PANO_F32}
 
 
+def _cuda_image_list(fn, items, nouns, spec, min_side, ndim=3):
+    """the sources of a gather: a non-empty list of (H, W, 3) CUDA tensors (ndim=4: the one tensor (B, H, W, 3)) of one dtype and one device with
+    H, W >= min_side -> (list, device with its index).  nouns = (a source, sources); spec: the shape as the message words it"""
+    if not items:
+        raise ValueError(f"{fn} needs at least one {nouns[0]}")
+    if not all(torch.is_tensor(p) for p in items):
+        raise TypeError(f"{fn} takes torch tensors as {nouns[1]}")
+    if not all(p.is_cuda for p in items):
+        raise PfError(f"{fn} runs on the GPU only (no CPU path)")
+    for p in items:
+        if p.dim() != ndim or p.shape[-1] != 3 or p.shape[-2] < min_side or p.shape[-3] < min_side:
+            raise ValueError(f"{spec}; got {tuple(p.shape)}")
+        if p.dtype not in _PANO_DTYPES:
+            raise ValueError(f"{nouns[1]} must be uint8 or float32; got {p.dtype}")
+    if len({p.dtype for p in items}) != 1 or len({p.device for p in items}) != 1:
+        raise ValueError(f"{fn}: all {nouns[1]} must have one dtype and one device")
+    dev = items[0].device
+    return items, dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _broadcast_len(fn, ts):
+    """the batch size that checked parameter tensors (numbers or 1-d) broadcast to, 1 when all are scalars; nothing moves to the device"""
+    try:
+        shape = torch.broadcast_shapes(*[tuple(t.shape) for t in ts])
+    except RuntimeError as e:
+        raise ValueError(f"{fn}: camera parameters do not broadcast: {e}") from None
+    return int(shape[0]) if shape else 1
+
+
+def _camera_rows(ts, angles, B, dev, mode):
+    """parameter tensors that broadcast to B -> (B, len(ts)) fp32 rows on the device, after every check of the caller.  As fields_from_params:
+    the `angles` columns go from degrees to radians in fp64 (mode "deg"), then everything to fp32"""
+    ts = [t.to(device=dev, dtype=torch.float64) for t in ts]
+    if mode == "deg":
+        for k in angles:
+            ts[k] = torch.deg2rad(ts[k])
+    return torch.stack([t.expand(B) for t in ts], 1).to(torch.float32)
+
+
+def _source_arrays(srcs, sizes, idx):
+    """the ctypes arguments that name a gather's sources: their pointers, their (H, W) pairs, the source of each output"""
+    n = len(srcs)
+    return ((ctypes.c_void_p * n)(*[p.data_ptr() for p in srcs]), (ctypes.c_int32 * (2 * n))(*[s for hw in sizes for s in hw]),
+            (ctypes.c_int32 * len(idx))(*idx))
+
+
 def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0.0, xi=0.0, height, width, pano_index=None, mode="deg", fields=True):
     """Equirectangular panoramas -> camera views and their ground-truth perspective fields on the GPU: the reference's labelled-data
     tooling (PanoCam.get_image / crop_equi, crop_distortion for the Unified Spherical Model, get_up_general / get_lat_general in
@@ -1122,39 +1168,20 @@ def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0
     GPU only: CPU panoramas raise PfError."""
     from .engine import _check, _stream_ptr, load_library
 
-    panos = [pano] if torch.is_tensor(pano) else list(pano)
-    if not panos:
-        raise ValueError("crop_panorama needs at least one panorama")
-    if not all(torch.is_tensor(p) for p in panos):
-        raise TypeError("crop_panorama takes torch tensors as panoramas")
-    if not all(p.is_cuda for p in panos):
-        raise PfError("crop_panorama runs on the GPU only (no CPU path)")
-    for p in panos:
-        if p.dim() != 3 or p.shape[2] != 3 or p.shape[0] < 2 or p.shape[1] < 2:
-            raise ValueError(f"a panorama must be (Hp, Wp, 3) with Hp, Wp >= 2; got {tuple(p.shape)}")
-        if p.dtype not in _PANO_DTYPES:
-            raise ValueError(f"panoramas must be uint8 or float32; got {p.dtype}")
-    if len({p.dtype for p in panos}) != 1 or len({p.device for p in panos}) != 1:
-        raise ValueError("crop_panorama: all panoramas must have one dtype and one device")
+    panos, dev = _cuda_image_list("crop_panorama", [pano] if torch.is_tensor(pano) else list(pano), ("panorama", "panoramas"),
+                                  "a panorama must be (Hp, Wp, 3) with Hp, Wp >= 2", 2)
     H, W = int(height), int(width)
     if H < 1 or W < 1:
         raise ValueError(f"crop size must be at least 1 x 1; got {H} x {W}")
     if mode not in ("deg", "rad"):
         raise ValueError("mode must be 'deg' or 'rad'")
-    dev = panos[0].device
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
     ts = []   # validated where they are; moved to the device after every check
     for name, v in (("roll", roll), ("pitch", pitch), ("yaw", yaw), ("rel_focal", rel_focal), ("rel_cx", rel_cx), ("rel_cy", rel_cy), ("xi", xi)):
         t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float64))
         if t.dim() > 1:
             raise ValueError(f"{name} must be a number or a 1-d sequence; got shape {tuple(t.shape)}")
         ts.append(t)
-    try:
-        shape = torch.broadcast_shapes(*[tuple(t.shape) for t in ts])
-    except RuntimeError as e:
-        raise ValueError(f"crop_panorama: camera parameters do not broadcast: {e}") from None
-    B = int(shape[0]) if shape else 1
+    B = _broadcast_len("crop_panorama", ts)
     if B < 1:
         raise ValueError("crop_panorama needs at least one crop")
     if pano_index is None:
@@ -1165,21 +1192,15 @@ def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0
             raise ValueError(f"pano_index has {len(idx)} entries for {B} crops")
         if any(i < 0 or i >= len(panos) for i in idx):
             raise ValueError(f"pano_index entries must be in [0, {len(panos)})")
-    ts = [t.to(device=dev, dtype=torch.float64) for t in ts]   # as fields_from_params: degrees -> radians in fp64, then fp32
-    if mode == "deg":
-        ts[0], ts[1], ts[2] = torch.deg2rad(ts[0]), torch.deg2rad(ts[1]), torch.deg2rad(ts[2])
-    cam = torch.stack([t.expand(B) for t in ts], 1).to(torch.float32).contiguous()
+    cam = _camera_rows(ts, (0, 1, 2), B, dev, mode).contiguous()
     panos = [p.contiguous() for p in panos]
     img = torch.empty((B, H, W, 3), dtype=panos[0].dtype, device=dev)
     up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if fields else None
     lat = torch.empty((B, H, W), dtype=torch.float32, device=dev) if fields else None
-    n = len(panos)
-    p_pano = (ctypes.c_void_p * n)(*[p.data_ptr() for p in panos])
-    hw = (ctypes.c_int32 * (2 * n))(*[s for p in panos for s in (int(p.shape[0]), int(p.shape[1]))])
-    c_idx = (ctypes.c_int32 * B)(*idx)
+    p_pano, hw, c_idx = _source_arrays(panos, [(int(p.shape[0]), int(p.shape[1])) for p in panos], idx)
     lib = load_library()
     with torch.cuda.device(dev):
-        _check(lib.pf_pano_crop(dev.index, n, p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, cam.data_ptr(), H, W, img.data_ptr(),
+        _check(lib.pf_pano_crop(dev.index, len(panos), p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, cam.data_ptr(), H, W, img.data_ptr(),
                                 up.data_ptr() if fields else None, lat.data_ptr() if fields else None, _stream_ptr()), None, "pf_pano_crop")
     return img, up, lat
 
@@ -1226,20 +1247,9 @@ def reproject_image(images, src, dst, *, height=None, width=None, src_index=None
     from .engine import _check, _stream_ptr, load_library
 
     batched = torch.is_tensor(images) and images.dim() == 4   # (B, Hs, Ws, 3): only as one tensor, not inside a list
-    srcs = [images] if torch.is_tensor(images) else list(images)
-    if not srcs or (batched and images.shape[0] < 1):
-        raise ValueError("reproject_image needs at least one image")
-    if not all(torch.is_tensor(p) for p in srcs):
-        raise TypeError("reproject_image takes torch tensors as images")
-    if not all(p.is_cuda for p in srcs):
-        raise PfError("reproject_image runs on the GPU only (no CPU path)")
-    for p in srcs:
-        if p.dim() != (4 if batched else 3) or p.shape[-1] != 3 or p.shape[-2] < 1 or p.shape[-3] < 1:
-            raise ValueError(f"an image must be (Hs, Ws, 3) with Hs, Ws >= 1, or a tensor (B, Hs, Ws, 3); got {tuple(p.shape)}")
-        if p.dtype not in _PANO_DTYPES:
-            raise ValueError(f"images must be uint8 or float32; got {p.dtype}")
-    if len({p.dtype for p in srcs}) != 1 or len({p.device for p in srcs}) != 1:
-        raise ValueError("reproject_image: all images must have one dtype and one device")
+    srcs = [] if batched and images.shape[0] < 1 else [images] if torch.is_tensor(images) else list(images)
+    srcs, dev = _cuda_image_list("reproject_image", srcs, ("image", "images"), "an image must be (Hs, Ws, 3) with Hs, Ws >= 1, or a tensor (B, Hs, Ws, 3)", 1,
+                                 ndim=4 if batched else 3)
     n = int(srcs[0].shape[0]) if batched else len(srcs)
     sizes = [(int(srcs[0].shape[1]), int(srcs[0].shape[2]))] * n if batched else [(int(p.shape[0]), int(p.shape[1])) for p in srcs]
     if height is None or width is None:
@@ -1253,11 +1263,7 @@ def reproject_image(images, src, dst, *, height=None, width=None, src_index=None
         raise ValueError("mode must be 'deg' or 'rad'")
     fill = float(fill)
     ts = _camera_params("src", src) + _camera_params("dst", dst)
-    try:
-        shape = torch.broadcast_shapes(*[tuple(t.shape) for t in ts])
-    except RuntimeError as e:
-        raise ValueError(f"reproject_image: camera parameters do not broadcast: {e}") from None
-    Bp = int(shape[0]) if shape else 1
+    Bp = _broadcast_len("reproject_image", ts)
     if src_index is not None:
         idx = [operator.index(i) for i in (src_index.tolist() if torch.is_tensor(src_index) else src_index)]
         if any(i < 0 or i >= n for i in idx):
@@ -1269,15 +1275,8 @@ def reproject_image(images, src, dst, *, height=None, width=None, src_index=None
         raise ValueError("reproject_image needs at least one output")
     if Bp not in (1, B):
         raise ValueError(f"reproject_image: camera parameters of length {Bp} for {B} outputs")
-    dev = srcs[0].device
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    ts = [t.to(device=dev, dtype=torch.float64) for t in ts]   # as crop_panorama: degrees -> radians in fp64, then fp32
-    if mode == "deg":
-        for k in (0, 1, 2, 7, 8, 9):
-            ts[k] = torch.deg2rad(ts[k])
-    cam_s = torch.stack([t.expand(B) for t in ts[:7]], 1).to(torch.float32).contiguous()
-    cam_d = torch.stack([t.expand(B) for t in ts[7:]], 1).to(torch.float32).contiguous()
+    cam = _camera_rows(ts, (0, 1, 2, 7, 8, 9), B, dev, mode)
+    cam_s, cam_d = cam[:, :7].contiguous(), cam[:, 7:].contiguous()
     if batched:
         whole = srcs[0].contiguous()
         srcs = [whole[i] for i in range(n)]
@@ -1286,9 +1285,7 @@ def reproject_image(images, src, dst, *, height=None, width=None, src_index=None
     img = torch.empty((B, H, W, 3), dtype=srcs[0].dtype, device=dev)
     valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_valid else None
     cmap = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if return_map else None
-    p_src = (ctypes.c_void_p * n)(*[p.data_ptr() for p in srcs])
-    hw = (ctypes.c_int32 * (2 * n))(*[s for hw_ in sizes for s in hw_])
-    c_idx = (ctypes.c_int32 * B)(*idx)
+    p_src, hw, c_idx = _source_arrays(srcs, sizes, idx)
     lib = load_library()
     with torch.cuda.device(dev):
         _check(lib.pf_reproject(dev.index, n, p_src, hw, _PANO_DTYPES[srcs[0].dtype], B, c_idx, cam_s.data_ptr(), cam_d.data_ptr(), H, W, fill,

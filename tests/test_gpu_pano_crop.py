@@ -1,6 +1,7 @@
 """Panorama crops on the GPU (include/pf_hip.h pf_pano_crop, perspectivefields_amd.crop_panorama) against the fp64 reference of
 tests/test_pano_crop_ref.py: geometry on a panorama of unit vectors, the uint8 path, the labels (bit-identical to fields_from_params
 at xi = 0), batch invariance, a camera-fit round trip, CUDA uint8 tensors as inference_batch input, and the chain end to end."""
+import ctypes
 import itertools
 
 import numpy as np
@@ -230,3 +231,32 @@ def test_crop_infer_fit_end_to_end(version):
         assert p["pred_gravity_original"].shape == (2, H, W) and p["pred_latitude_original"].shape == (H, W)
     fits = m.fit_camera(preds)
     assert len(fits) == B and all(d["pred_roll"].shape == () for d in fits)
+
+
+@pytest.mark.parametrize("dtype", [torch.uint8, torch.float32])
+def test_unaligned_outputs_take_the_scalar_stores_and_give_the_same_bits(dtype):
+    """crop_panorama allocates its outputs itself, always aligned; storage that is not 16-byte aligned reaches pf_pano_crop only through the
+    C interface, called here directly: W = 56 with aligned outputs (vector stores) against the same call into buffers shifted by one element
+    (scalar stores).  20 x 56 is less than one 64 x 16 tile across and not a whole number of tiles down; xi = 0 takes the pinhole labels,
+    xi > 0 the spherical ones, and at xi = 1.2 with this focal length the corners have no ray (image 0, labels NaN)"""
+    from perspectivefields_amd.engine import _check, load_library
+
+    H, W, B = 20, 56, 5
+    cases = [(12.0, 20.0, 30.0, 0.6, 0.0, 0.0, 0.0), (-25.0, -40.0, -100.0, 0.9, 0.1, -0.08, 0.0), (8.0, 35.0, 170.0, 0.5, 0.0, 0.0, 0.8),
+             (-15.0, -10.0, 60.0, 0.7, -0.05, 0.1, 0.8), (20.0, 5.0, -20.0, 0.3, 0.0, 0.0, 1.2)]
+    pano = torch.from_numpy(np.random.default_rng(21).integers(0, 256, (64, 128, 3), dtype=np.uint8)).cuda().to(dtype)
+    img, up, lat = crop(pano, cases, H, W)
+    assert torch.isnan(lat[4]).any() and not torch.isnan(lat[4]).all() and not torch.isnan(lat[:4]).any()
+    cam = torch.from_numpy(np.asarray([theta_rad(*c) for c in cases])).cuda().float().contiguous()
+    n = B * H * W
+    img2 = torch.zeros(n * 3 + 1, dtype=dtype, device="cuda")
+    up2 = torch.zeros(n * 2 + 1, dtype=torch.float32, device="cuda")
+    lat2 = torch.zeros(n + 1, dtype=torch.float32, device="cuda")
+    _check(load_library().pf_pano_crop(0, 1, (ctypes.c_void_p * 1)(pano.data_ptr()), (ctypes.c_int32 * 2)(64, 128), 0 if dtype == torch.uint8 else 1, B,
+                                       (ctypes.c_int32 * B)(*([0] * B)), cam.data_ptr(), H, W, img2[1:].data_ptr(), up2[1:].data_ptr(), lat2[1:].data_ptr(),
+                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), None, "pf_pano_crop")
+    assert img2[1:].data_ptr() % (4 if dtype == torch.uint8 else 16) != 0
+    assert torch.equal(_bits(img2[1:].reshape(img.shape)), _bits(img))
+    assert torch.equal(_bits(up2[1:].reshape(up.shape)), _bits(up))
+    assert torch.equal(_bits(lat2[1:].reshape(lat.shape)), _bits(lat))
+    assert img2[0] == 0 and up2[0] == 0 and lat2[0] == 0   # nothing written in front of the buffers
