@@ -450,6 +450,41 @@ int pf_reproject(int device, int n_src, const void* const* h_src, const int32_t*
                  int batch, const int32_t* h_src_index /*[batch]*/, const float* d_cam_src7 /*[batch][7]*/, const float* d_cam_dst7 /*[batch][7]*/,
                  int H, int W, float fill, void* d_img, uint8_t* d_valid /*or NULL*/, float* d_map /*or NULL*/, void* stream);
 
+/* Camera views of one centre composed into equirectangular panoramas on the device: the inverse direction of pf_pano_crop, several views
+ * blended per panorama pixel (pano_compose.hip).
+ * Per view theta = d_cam7 row = {roll r, pitch p, yaw psi (RADIANS), rel_focal f, rel_cx cx, rel_cy cy, xi}, exactly as in pf_reproject: F = f*Hs,
+ * Cx = (cx + 1/2)*Ws, Cy = (cy + 1/2)*Hs of the view's own image Hs x Ws, R = R_pitch(p) R_roll(r) camera -> world, and the yaw turn Y(psi).
+ * For pixel (row, col) of an Hp x Wp panorama (the inverse of pf_pano_crop's step from ray to pixel):
+ *   lon = ((col + 1/2)/Wp - 1/2) 2 pi, lat = (1/2 - (row + 1/2)/Hp) pi, D = (cos lat sin lon, -sin lat, cos lat cos lon)
+ * and for each view i of that panorama, in the caller's order:
+ *   1 ray       X = M_i D, M_i = R_i^T Y(-psi_i), computed once per view on the device
+ *   2 visible   iff X.z > z_min(xi_i) (pf_reproject's step 3)
+ *   3 point     (a, b) = F_i (X.x, X.y) / (X.z + xi_i |X|) + (Cx_i, Cy_i), pixel-edge units
+ *   4 covered   d = min(a, Ws_i - a, b, Hs_i - b); the view covers the pixel iff it is visible and d > 0, a positive comparison: a NaN or
+ *               infinite coordinate (non-finite parameters) covers nothing and issues no load
+ *   5 weight    blend = PF_BLEND_FEATHER: w_i = min(2 d / min(Hs_i, Ws_i), 1), 0 on the view's border and 1 in the middle of its short side;
+ *               blend = PF_BLEND_MEAN: w_i = 1
+ *   6 colour    c_i = bilinear at (a - 1/2, b - 1/2), the four taps clamped into the view (pf_reproject's step 6)
+ * S = sum w_i and C = sum w_i c_i, accumulated in fp32 in view order.  The pixel is C / S where S > 0, else `fill`; PF_PANO_U8: rounded half up and
+ * clamped to [0, 255] (`fill` converted like a value).  d_weight, when given, holds S (0 for an uncovered pixel).
+ * The feather weight falls to 0 at a view's border, so the composite is continuous across view borders; MEAN with one view is the bilinear sample.
+ * Each output value depends on its own panorama's views, their order and the options only: the same bits in any batch and on every run; a view
+ * with non-finite parameters contributes nothing and leaves every other bit unchanged.  No antialiasing: a strongly minified view aliases.
+ * h_view = HOST array of n_view DEVICE pointers, (Hs, Ws, 3) channel-interleaved, all of type `dtype`; h_view_hw = HOST [n_view][2] (Hs, Ws), each
+ * >= 1; h_view_pano = HOST [n_view], the panorama of each view, non-decreasing, in [0, n_pano) (a panorama without views is all `fill`, weight 0).
+ * d_pano = DEVICE [n_pano][Hp][Wp][3] of `dtype` (required); d_weight = DEVICE [n_pano][Hp][Wp] fp32 or NULL; d_acc = DEVICE [n_pano][Hp][Wp][4]
+ * fp32 workspace, 16-byte aligned, needed only when a panorama has more than 32 views (its partial (C, S) travel through it between launches).
+ * Argument errors (NULL required pointers, n_view < 1, n_pano < 1, a view side < 1, Hp or Wp < 1, a bad dtype or blend, an index out of range or
+ * decreasing, d_acc missing when it is needed) return PF_ERR_ARG before any device work.  Panoramas share launches of at most 32 views and 32
+ * panoramas; a panorama of n > 32 views takes ceil(n / 32) launches of its own.  All on `stream`, no host synchronisation; stateless, no handle. */
+#define PF_BLEND_FEATHER 0
+#define PF_BLEND_MEAN 1
+int pf_pano_compose(int device, int n_view, const void* const* h_view, const int32_t* h_view_hw /*[n_view][2]*/, int dtype,
+                    const int32_t* h_view_pano /*[n_view], non-decreasing, in [0, n_pano)*/, const float* d_cam7 /*[n_view][7]*/,
+                    int n_pano, int Hp, int Wp, int blend /*PF_BLEND_FEATHER|PF_BLEND_MEAN*/, float fill,
+                    void* d_pano /*[n_pano][Hp][Wp][3]*/, float* d_weight /*[n_pano][Hp][Wp] or NULL*/,
+                    float* d_acc /*[n_pano][Hp][Wp][4] fp32 workspace; may be NULL unless a panorama has more than 32 views*/, void* stream);
+
 /* Predicted perspective fields against ground truth on the device: per-pixel errors, per-image statistics with an exact median, and
  * a running histogram for dataset statistics (field_err.hip).
  * Inputs per image: up_pred, up_gt [2][H][W] and lat_pred, lat_gt [H][W] degrees, fp32 (the layout of pred_gravity_original /

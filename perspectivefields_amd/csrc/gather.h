@@ -1,4 +1,4 @@
-// What the batched image gathers (pano_crop.hip, reproject.hip) share on the device: the bilinear blend of four taps, the uint8 rounding rule and
+// What the batched image gathers (pano_crop.hip, reproject.hip, pano_compose.hip) share on the device: the bilinear blend of four taps, the uint8 rounding rule and
 // the stores of the RGB epilogue.  Each kernel keeps its camera model and its index policy (which taps); the blend's order of operations and the
 // rounding are here alone, so that every gather gives the same bits for the same taps.  The launch's shape is GatherDims (pf_kernels.h).
 // Two pieces stay in the kernels because no helper form of them compiled to the kernels' instructions: the four lines of
@@ -26,6 +26,17 @@ __device__ __forceinline__ void bilerp_rgb(const T* __restrict__ src, int Ws, in
     const float bot = (1.f - fu) * texel(src, i10 + k) + fu * texel(src, i11 + k);
     out[k] = (1.f - fv) * top + fv * bot;
   }
+}
+
+// bilinear sample of channel-interleaved (Hs, Ws, 3) texels at (u, v), pixel centres at integers; the taps clamp into the image
+template <typename T>
+__device__ __forceinline__ void sample_clamped(const T* __restrict__ src, int Hs, int Ws, float u, float v, float* out) {
+  const float uf = floorf(u), vf = floorf(v);
+  const float fu = u - uf, fv = v - vf;
+  const int c = (int)uf, r = (int)vf;
+  const int c0 = min(max(c, 0), Ws - 1), c1 = min(max(c + 1, 0), Ws - 1);
+  const int r0 = min(max(r, 0), Hs - 1), r1 = min(max(r + 1, 0), Hs - 1);
+  bilerp_rgb(src, Ws, r0, r1, c0, c1, fu, fv, out);
 }
 
 // uint8 of an fp32 value: rounded half up, clamped to [0, 255]

@@ -1,5 +1,5 @@
-// Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the two image
-// gathers (pano_crop.hip, reproject.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -98,6 +98,76 @@ int pf_reproject(int device, int n_src, const void* const* src, const int32_t* s
                       rb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
                       rb.map = d_map ? d_map + (size_t)i0 * 2 * npx : nullptr;
                     });
+}
+
+// Several views per output, so not gather_run: the launches follow the panoramas, not the sources.  Panoramas share a launch while it holds at most
+// ComposeBatch::MAX views and MAX panoramas; a panorama of more views takes launches of its own that hand (C, S) on through d_acc
+int pf_pano_compose(int device, int n_view, const void* const* view, const int32_t* view_hw, int dtype, const int32_t* view_pano, const float* d_cam7,
+                    int n_pano, int Hp, int Wp, int blend, float fill, void* d_pano, float* d_weight, float* d_acc, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_pano_compose: " + m; return PF_ERR_ARG; };
+  constexpr int MAX = ComposeBatch::MAX;
+  if (n_view < 1 || !view || !view_hw) return bad("needs at least one view (h_view, h_view_hw)");
+  if (dtype != PF_PANO_U8 && dtype != PF_PANO_F32) return bad(fmt("unknown dtype %d", dtype));
+  if (blend != PF_BLEND_FEATHER && blend != PF_BLEND_MEAN) return bad(fmt("unknown blend %d", blend));
+  for (int k = 0; k < n_view; ++k) {
+    if (!view[k]) return bad(fmt("NULL pointer of view %d", k));
+    if (view_hw[2 * k] < 1 || view_hw[2 * k + 1] < 1) return bad(fmt("view %d is %d x %d, smaller than 1 x 1", k, view_hw[2 * k], view_hw[2 * k + 1]));
+  }
+  if (n_pano < 1 || !view_pano || !d_cam7 || !d_pano) return bad("n_pano >= 1, h_view_pano, d_cam7 and d_pano are required");
+  if (Hp < 1 || Wp < 1) return bad(fmt("panorama size %d x %d", Hp, Wp));
+  std::vector<int> count(n_pano, 0);
+  for (int k = 0; k < n_view; ++k) {
+    if (view_pano[k] < 0 || view_pano[k] >= n_pano) return bad(fmt("view %d: panorama index %d of %d", k, view_pano[k], n_pano));
+    if (k > 0 && view_pano[k] < view_pano[k - 1]) return bad(fmt("view %d: panorama index %d after %d, the indices must not decrease", k, view_pano[k], view_pano[k - 1]));
+    ++count[view_pano[k]];
+  }
+  const bool carry = *std::max_element(count.begin(), count.end()) > MAX;
+  if (carry && !d_acc) return bad(fmt("d_acc is required: a panorama has more than %d views", MAX));
+  if (carry && misalign(d_acc, 15)) return bad("d_acc must be aligned to 16 bytes");
+  const int tpr = 16;  // a 64 x 16 pixel tile, as the other gathers
+  const long tiles_x = (Wp + 4 * tpr - 1) / (4 * tpr), tiles_y = (Hp + 256 / tpr - 1) / (256 / tpr);
+  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("panorama size %d x %d too large", Hp, Wp));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  const size_t esz = dtype == PF_PANO_U8 ? 1 : 4, npx = (size_t)Hp * Wp;
+  const int vec = (Wp % 4 == 0 && (misalign(d_pano, dtype == PF_PANO_U8 ? 3 : 15) | misalign(d_weight, 15)) == 0) ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the launch of the panoramas [p0, p0 + np) that reads the views [v0, v0 + nv): all views of those panoramas, or (np == 1) one slice of a panorama's
+  auto launch = [&](int p0, int np, int v0, int nv, uint32_t carry_in, uint32_t carry_out) {
+    ComposeBatch cb;
+    cb.d = GatherDims{np, Hp, Wp, tpr, (int)tiles_x, (int)tiles_y, vec};
+    cb.fill = fill;
+    for (int k = 0; k < nv; ++k) {
+      cb.src.p[k] = view[v0 + k];
+      cb.src.H[k] = view_hw[2 * (v0 + k)]; cb.src.W[k] = view_hw[2 * (v0 + k) + 1];
+    }
+    cb.cam = d_cam7 + (size_t)v0 * 7;
+    for (int k = 0, f = 0; k < np; ++k) {
+      cb.first[k] = f;
+      cb.count[k] = np == 1 ? nv : count[p0 + k];
+      f += cb.count[k];
+    }
+    cb.carry_in = carry_in; cb.carry_out = carry_out;
+    cb.img = static_cast<char*>(d_pano) + (size_t)p0 * npx * 3 * esz;
+    cb.weight = d_weight ? d_weight + (size_t)p0 * npx : nullptr;
+    cb.acc = d_acc ? d_acc + (size_t)p0 * npx * 4 : nullptr;
+    launch_pano_compose(cb, dtype, blend, s);
+  };
+  int p0 = 0, np = 0, v0 = 0, nv = 0;  // the shared launch being filled
+  for (int p = 0, v = 0; p < n_pano; v += count[p], ++p) {
+    const int c = count[p];
+    if (np > 0 && (c > MAX || nv + c > MAX || np == MAX)) { launch(p0, np, v0, nv, 0u, 0u); np = nv = 0; }
+    if (c > MAX) {
+      for (int i = 0; i < c; i += MAX) launch(p, 1, v + i, std::min(c - i, MAX), i > 0 ? 1u : 0u, i + MAX < c ? 1u : 0u);
+      continue;
+    }
+    if (np == 0) { p0 = p; v0 = v; }
+    ++np; nv += c;
+  }
+  if (np > 0) launch(p0, np, v0, nv, 0u, 0u);
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_pano_compose: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
 }
 
 // workspace of pf_fit_camera / pf_fit_camera_usm: per-image LM state, then every image's partial records, each region 256-byte aligned.

@@ -484,6 +484,23 @@ void launch_reproject(const ReprojBatch& rb, int dtype, hipStream_t s);
 static_assert(sizeof(PanoBatch) == 576 && offsetof(PanoBatch, src) == 32, "PanoBatch layout");
 static_assert(sizeof(ReprojBatch) == 584 && offsetof(ReprojBatch, fill) == 28 && offsetof(ReprojBatch, src) == 32, "ReprojBatch layout");
 
+// camera views of one centre -> equirectangular panoramas (pano_compose.hip, include/pf_hip.h pf_pano_compose): the outputs of a launch are up to MAX
+// panoramas, its sources up to MAX views; panorama k blends the views [first[k], first[k] + count[k]) of the launch in that order
+struct ComposeBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;       // n panoramas of Hp x Wp
+  float fill;         // value of a pixel that no view covers
+  GatherSources src;  // the launch's views (Hs, Ws, 3)
+  const float* cam;   // [views of the launch][7]: roll, pitch, yaw (radians), rel_focal, rel_cx, rel_cy, xi
+  int first[MAX], count[MAX];
+  uint32_t carry_in, carry_out;  // bit k: panorama k starts from / ends in the accumulator (a panorama of more than MAX views, one launch per MAX views)
+  void* img;      // [n][Hp][Wp][3], the views' type
+  float* weight;  // NULL or [n][Hp][Wp]: the summed weight S
+  float* acc;     // NULL or [n][Hp][Wp][4]: (C.r, C.g, C.b, S) between the launches of one panorama
+};
+void launch_pano_compose(const ComposeBatch& cb, int dtype, int blend, hipStream_t s);
+static_assert(offsetof(ComposeBatch, d) == 0 && offsetof(ComposeBatch, src) == 32, "ComposeBatch layout");
+
 // predicted fields against ground truth (field_err.hip, include/pf_hip.h pf_field_errors): up to FerrBatch::MAX images per launch,
 // per-image sizes and pointers in the kernel arguments
 constexpr int FERR_REC = 10;         // doubles of one accumulate block's partial record

@@ -32,17 +32,6 @@ struct ReprojConsts {
   float Fs, Cxs, Cys, xis, zmin;
 };
 
-// bilinear sample of channel-interleaved (Hs, Ws, 3) texels at (u, v), pixel centres at integers; the taps clamp into the image
-template <typename T>
-__device__ __forceinline__ void sample_clamped(const T* __restrict__ src, int Hs, int Ws, float u, float v, float* out) {
-  const float uf = floorf(u), vf = floorf(v);
-  const float fu = u - uf, fv = v - vf;
-  const int c = (int)uf, r = (int)vf;
-  const int c0 = min(max(c, 0), Ws - 1), c1 = min(max(c + 1, 0), Ws - 1);
-  const int r0 = min(max(r, 0), Hs - 1), r1 = min(max(r + 1, 0), Hs - 1);
-  bilerp_rgb(src, Ws, r0, r1, c0, c1, fu, fv, out);
-}
-
 }  // namespace
 
 template <typename T, bool EXTRAS>

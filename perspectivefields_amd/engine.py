@@ -70,6 +70,7 @@ _SIGNATURES = {
     "pf_fields_from_params_usm": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _P, _P, _P]),
     "pf_pano_crop": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     "pf_reproject": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _P, _P, _P, _P]),
+    "pf_pano_compose": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P, _P, _P]),
     "pf_field_errors_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
     "pf_field_errors": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_float, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
     "pf_profile_begin": (_c.c_int, [_P, _c.c_uint]),

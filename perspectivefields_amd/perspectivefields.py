@@ -498,6 +498,27 @@ class PerspectiveFields(nn.Module):
         ups, lats = [p["pred_gravity_original"] for p in plist], [p["pred_latitude_original"] for p in plist]
         return field_errors(ups[0], lats[0], up_gt, lat_gt, **kw) if single else field_errors(ups, lats, up_gt, lat_gt, **kw)
 
+    @staticmethod
+    def _pred_cameras(fn, preds):
+        """the cameras of inference* / fit_camera results as a dict of one column per parameter (degrees), on the device where the results hold tensors"""
+        plist = [preds] if isinstance(preds, dict) else list(preds)
+        if not plist:
+            raise ValueError(f"{fn} needs at least one result dict")
+        for p in plist:
+            if any(k not in p for k in ("pred_roll", "pred_pitch", "pred_rel_focal")):
+                raise PfError(f"{fn} needs camera parameters (pred_roll, pred_pitch, pred_rel_focal) and this result has none: a PersNet "
+                              "model predicts fields only; pass the result of fit_camera(preds) instead")
+
+        def column(key):  # one value per result
+            vals = [p.get(key, 0.0) for p in plist]
+            tens = [v for v in vals if torch.is_tensor(v)]
+            if not tens:
+                return np.asarray(vals, dtype=np.float64)
+            return torch.stack([v.reshape(()).to(device=tens[0].device, dtype=torch.float64) if torch.is_tensor(v)
+                                else torch.tensor(float(v), dtype=torch.float64, device=tens[0].device) for v in vals])
+
+        return {k: column("pred_" + k) for k in ("roll", "pitch", "rel_focal", "rel_cx", "rel_cy", "xi")}
+
     def rectify(self, images, preds, *, level="roll", undistort=True, rel_focal=None, height=None, width=None, **kw):
         """The images warped with their recovered cameras, on the GPU (see reproject_image for `images`, the other options --
         src_index, fill, return_valid, return_map -- and what is returned).  preds: one result dict, or a list of them, of inference*
@@ -513,26 +534,21 @@ class PerspectiveFields(nn.Module):
             raise ValueError("level must be 'roll', 'full' or 'none'")
         if "mode" in kw:
             raise ValueError("rectify takes the angles of its preds, which are degrees: no mode")
-        plist = [preds] if isinstance(preds, dict) else list(preds)
-        if not plist:
-            raise ValueError("rectify needs at least one result dict")
-        for p in plist:
-            if any(k not in p for k in ("pred_roll", "pred_pitch", "pred_rel_focal")):
-                raise PfError("rectify needs camera parameters (pred_roll, pred_pitch, pred_rel_focal) and this result has none: a PersNet "
-                              "model predicts fields only; pass the result of fit_camera(preds) instead")
-
-        def column(key):  # one value per result, on the device where the results hold tensors
-            vals = [p.get(key, 0.0) for p in plist]
-            tens = [v for v in vals if torch.is_tensor(v)]
-            if not tens:
-                return np.asarray(vals, dtype=np.float64)
-            return torch.stack([v.reshape(()).to(device=tens[0].device, dtype=torch.float64) if torch.is_tensor(v)
-                                else torch.tensor(float(v), dtype=torch.float64, device=tens[0].device) for v in vals])
-
-        src = {k: column("pred_" + k) for k in ("roll", "pitch", "rel_focal", "rel_cx", "rel_cy", "xi")}
+        src = PerspectiveFields._pred_cameras("rectify", preds)
         dst = dict(roll=src["roll"] if level == "none" else 0.0, pitch=0.0 if level == "full" else src["pitch"],
                    rel_focal=src["rel_focal"] if rel_focal is None else rel_focal, xi=0.0 if undistort else src["xi"])
         return reproject_image(images, src, dst, height=height, width=width, mode="deg", **kw)
+
+    def compose_panorama(self, images, preds, *, yaw=0.0, **kw):
+        """The images placed on equirectangular panoramas with their recovered cameras, on the GPU (see compose_panorama for `images`, the
+        options -- height, width, pano_index, n_pano, blend, fill, return_weight -- and what is returned).  preds: one result dict, or a
+        list of them, of inference* (a ParamNet model) or of fit_camera, one per image, read as `rectify` reads them.  The fields say nothing
+        about the direction a view faces, so yaw (degrees; a number or one per image) is the caller's."""
+        if "mode" in kw:
+            raise ValueError("compose_panorama takes the angles of its preds, which are degrees: no mode")
+        cams = PerspectiveFields._pred_cameras("compose_panorama", preds)
+        cams["yaw"] = yaw
+        return compose_panorama(images, cams, mode="deg", **kw)
 
     def forward(self, batched_inputs) -> List[dict]:
         """batched_inputs: list of {"image": (3,320,320) float BGR 0..255, "height", "width"} (reference :223-272)."""
@@ -1209,14 +1225,14 @@ _CAM_KEYS = ("roll", "pitch", "yaw", "rel_focal", "rel_cx", "rel_cy", "xi")   # 
 _CAM_REQUIRED = ("roll", "pitch", "rel_focal")
 
 
-def _camera_params(what, cam):
+def _camera_params(what, cam, fn="reproject_image"):
     """a camera dict -> its seven values as tensors in the order of _CAM_KEYS, checked where they are (nothing moves to the device yet)"""
     if not isinstance(cam, Mapping):
-        raise TypeError(f"reproject_image: {what} must be a dict of camera parameters; got {type(cam).__name__}")
+        raise TypeError(f"{fn}: {what} must be a dict of camera parameters; got {type(cam).__name__}")
     unknown = [k for k in cam if k not in _CAM_KEYS]
     missing = [k for k in _CAM_REQUIRED if k not in cam]
     if unknown or missing:
-        raise ValueError(f"reproject_image: {what} needs {_CAM_REQUIRED} and may hold {_CAM_KEYS[2:3] + _CAM_KEYS[4:]}; unknown {unknown}, missing {missing}")
+        raise ValueError(f"{fn}: {what} needs {_CAM_REQUIRED} and may hold {_CAM_KEYS[2:3] + _CAM_KEYS[4:]}; unknown {unknown}, missing {missing}")
     ts = []
     for k in _CAM_KEYS:
         v = cam.get(k, 0.0)
@@ -1293,3 +1309,83 @@ def reproject_image(images, src, dst, *, height=None, width=None, src_index=None
                None, "pf_reproject")
     out = (img,) + ((valid.view(torch.bool),) if return_valid else ()) + ((cmap,) if return_map else ())
     return out[0] if len(out) == 1 else out
+
+
+BLEND_FEATHER, BLEND_MEAN = 0, 1
+_BLENDS = {"feather": BLEND_FEATHER, "mean": BLEND_MEAN}
+_COMPOSE_MAX_VIEWS = 32   # views of one panorama per launch (csrc/pf_kernels.h ComposeBatch::MAX); more need the accumulator
+
+
+def compose_panorama(images, cams, *, height, width, pano_index=None, n_pano=None, blend="feather", mode="deg", fill=0, return_weight=False):
+    """Camera views of one centre -> equirectangular panoramas on the GPU: the inverse direction of `crop_panorama`, with several views
+    blended per panorama pixel.  Model: include/pf_hip.h pf_pano_compose; the cameras and the panorama's
+    longitude / latitude convention are those of `crop_panorama`, so composing its crops gives the panorama back where they cover it.
+
+    images: what `reproject_image` takes -- a CUDA tensor (Hs, Ws, 3) or (B, Hs, Ws, 3), uint8 or float32, or a list of (Hs, Ws, 3) tensors of
+    one dtype and one device, whose sizes may differ.  cams: a dict with `roll`, `pitch`, `rel_focal` (required) and `yaw`, `rel_cx`,
+    `rel_cy`, `xi` (default 0); angles in degrees unless mode="rad"; each value a number, a 0-d tensor or a 1-d sequence / tensor of one
+    entry per view; device tensors stay on the device.
+    height, width: the size Hp x Wp of every panorama.  pano_index: None (one panorama from all views) or one integer per view, the panorama
+    it belongs to; the views are sorted by it on the host, stably, so the blend order within a panorama is the caller's.  n_pano: the
+    number of panoramas, default max(pano_index) + 1; a panorama without views is all `fill`.
+    blend: "feather" -- a view's weight falls linearly from 1 in the middle of its short side to 0 on its border, so the composite is
+    continuous across view borders; "mean" -- every covering view counts the same (one view: its bilinear sample).  fill: the value of
+    the pixels that no view covers.
+    Returns the panoramas (n_pano, Hp, Wp, 3) in the views' dtype; with return_weight=True also the summed weight (n_pano, Hp, Wp)
+    float32, 0 where nothing covers the pixel.  Bilinear sampling without antialiasing: a strongly minified view aliases.
+    GPU only: CPU images raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    batched = torch.is_tensor(images) and images.dim() == 4
+    srcs = [] if batched and images.shape[0] < 1 else [images] if torch.is_tensor(images) else list(images)
+    srcs, dev = _cuda_image_list("compose_panorama", srcs, ("view", "views"), "a view must be (Hs, Ws, 3) with Hs, Ws >= 1, or a tensor (B, Hs, Ws, 3)", 1,
+                                 ndim=4 if batched else 3)
+    n = int(srcs[0].shape[0]) if batched else len(srcs)
+    sizes = [(int(srcs[0].shape[1]), int(srcs[0].shape[2]))] * n if batched else [(int(p.shape[0]), int(p.shape[1])) for p in srcs]
+    Hp, Wp = int(height), int(width)
+    if Hp < 1 or Wp < 1:
+        raise ValueError(f"panorama size must be at least 1 x 1; got {Hp} x {Wp}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    if blend not in _BLENDS:
+        raise ValueError(f"blend must be one of {tuple(_BLENDS)}; got {blend!r}")
+    fill = float(fill)
+    ts = _camera_params("cams", cams, "compose_panorama")
+    Bp = _broadcast_len("compose_panorama", ts)
+    if Bp not in (1, n):
+        raise ValueError(f"compose_panorama: camera parameters of length {Bp} for {n} views")
+    if pano_index is None:
+        idx = [0] * n
+    else:
+        idx = [operator.index(i) for i in (pano_index.tolist() if torch.is_tensor(pano_index) else pano_index)]
+        if len(idx) != n:
+            raise ValueError(f"pano_index has {len(idx)} entries for {n} views")
+        if any(i < 0 for i in idx):
+            raise ValueError("pano_index entries must be >= 0")
+    P = max(idx) + 1 if n_pano is None else operator.index(n_pano)
+    if P < 1 or any(i >= P for i in idx):
+        raise ValueError(f"pano_index entries must be in [0, {P}) (n_pano)")
+    order = sorted(range(n), key=idx.__getitem__)   # stable: the caller's order within a panorama
+    cam = _camera_rows(ts, (0, 1, 2), n, dev, mode)
+    if order != list(range(n)):
+        cam = cam[torch.as_tensor(order, device=dev)]
+    cam = cam.contiguous()
+    if batched:
+        whole = srcs[0].contiguous()
+        srcs = [whole[i] for i in range(n)]
+    else:
+        srcs = [p.contiguous() for p in srcs]
+    srcs = [srcs[i] for i in order]
+    counts = [0] * P
+    for i in idx:
+        counts[i] += 1
+    pano = torch.empty((P, Hp, Wp, 3), dtype=srcs[0].dtype, device=dev)
+    weight = torch.empty((P, Hp, Wp), dtype=torch.float32, device=dev) if return_weight else None
+    acc = torch.empty((P, Hp, Wp, 4), dtype=torch.float32, device=dev) if max(counts) > _COMPOSE_MAX_VIEWS else None
+    p_src, hw, c_idx = _source_arrays(srcs, [sizes[i] for i in order], [idx[i] for i in order])
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_pano_compose(dev.index, n, p_src, hw, _PANO_DTYPES[srcs[0].dtype], c_idx, cam.data_ptr(), P, Hp, Wp, _BLENDS[blend], fill,
+                                   pano.data_ptr(), weight.data_ptr() if return_weight else None, acc.data_ptr() if acc is not None else None,
+                                   _stream_ptr()), None, "pf_pano_compose")
+    return (pano, weight) if return_weight else pano
