@@ -485,6 +485,44 @@ int pf_pano_compose(int device, int n_view, const void* const* h_view, const int
                     void* d_pano /*[n_pano][Hp][Wp][3]*/, float* d_weight /*[n_pano][Hp][Wp] or NULL*/,
                     float* d_acc /*[n_pano][Hp][Wp][4] fp32 workspace; may be NULL unless a panorama has more than 32 views*/, void* stream);
 
+/* The relative yaw of camera views of one centre, from the pictures: for ordered pairs (a, b) of views and a list of candidate turns, the moments of
+ * the two luminance images on their overlap, from which the zero-mean normalised cross-correlation follows (yaw_align.hip).
+ * The fields give roll, pitch and intrinsics of a view but not the direction it faces; with those known, two views of one centre differ by a single
+ * turn about the vertical, and the right turn is the one at which the pictures agree where they overlap.
+ * Per view theta = d_cam6 row = {roll r, pitch p (RADIANS), rel_focal f, rel_cx cx, rel_cy cy, xi}: pf_reproject's camera without the yaw, the same
+ * F, Cx, Cy of the view's own image, R = R_pitch(p) R_roll(r), Y(t), usm_ray, usm_project and z_min.
+ * For the ordered pair (a, b), the candidate D (radians) and the stride s, the samples are the pixels (row, col) of b with row % s == 0 and col % s == 0:
+ *   1 ray       X_b = the ray of (col + 1/2, row + 1/2) in b (pf_reproject's step 1); a pixel without a ray is no sample.  W = R_b X_b
+ *   2 turn      X_a = R_a^T Y(D) W: pf_reproject's M with a as the source at yaw 0 and b as the destination at yaw D, so the pictures agree at
+ *               D = yaw_b - yaw_a
+ *   3 visible   iff X_a.z > z_min(xi_a)
+ *   4 point     (p, q) = F_a (X_a.x, X_a.y) / (X_a.z + xi_a |X_a|) + (Cx_a, Cy_a), pixel-edge units
+ *   5 covered   iff visible and p > 0, Ws_a - p > 0, q > 0, Hs_a - q > 0: positive comparisons, a NaN or infinite coordinate (non-finite
+ *               parameters) covers nothing and issues no load
+ *   6 values    luminance L = 0.299 c0 + 0.587 c1 + 0.114 c2 - c of the channels as stored, c = 127.5 (PF_PANO_U8) or 0.5 (PF_PANO_F32); c conditions
+ *               the sums and leaves the correlation unchanged.  y = L_b at the pixel; x = L_a bilinear at (p - 1/2, q - 1/2), the four taps clamped
+ *               into a (pf_reproject's step 6)
+ * d_moments[pair][candidate] = {n, sum x, sum y, sum x^2, sum y^2, sum xy} over the covered samples, as fp64: fp32 sums over tiles of 1024 samples
+ * in sample order (row-major in b), the tiles added in order in fp64.  The caller's score is
+ *   ZNCC = (n sum xy - sum x sum y) / sqrt((n sum x^2 - (sum x)^2) (n sum y^2 - (sum y)^2))
+ * where both variances are positive; one below 2^-16 of n times its sum of squares is within the rounding of the fp32 sums and counts as 0.
+ * Every value depends on its pair's two views, their cameras, the candidate and the stride only: the same bits in any batch of pairs, for any
+ * split of the candidates over calls and on every run.  A view with non-finite parameters has n = 0 in all its pairs.
+ * h_view = HOST array of n_view (>= 2) DEVICE pointers, (H, W, 3) channel-interleaved, all of type `dtype`; h_view_hw = HOST [n_view][2] (H, W), each >= 1;
+ * d_cam6 = DEVICE [n_view][6]; h_pairs = HOST [n_pair][2] (a, b) view indices, a != b; d_cand = DEVICE [n_cand] fp32 radians, 1 <= n_cand <=
+ * PF_YAW_MAX_CAND; d_moments = DEVICE [n_pair][n_cand][6] fp64, 16-byte aligned; workspace of pf_yaw_moments_workspace_bytes (0 for arguments
+ * pf_yaw_moments rejects): a luminance plane per view, converted once per call, and the tiles' records.
+ * Argument errors (NULL pointers, n_view < 2, n_pair < 1, a view side < 1, an index out of range, a == b, stride < 1, n_cand out of range, a bad
+ * dtype, a small workspace, a misaligned d_moments) return PF_ERR_ARG before any device work.  One luminance launch per 32 views, a store launch
+ * and a sum launch per 64 pairs, all on `stream`, no atomics, no host synchronisation; stateless, no handle. */
+#define PF_YAW_MAX_CAND 4096
+size_t pf_yaw_moments_workspace_bytes(int n_view, const int32_t* h_view_hw /*[n_view][2]*/, int n_pair, const int32_t* h_pairs /*[n_pair][2]*/,
+                                      int n_cand, int stride);
+int pf_yaw_moments(int device, int n_view, const void* const* h_view, const int32_t* h_view_hw /*[n_view][2]*/, int dtype /*PF_PANO_U8|PF_PANO_F32*/,
+                   const float* d_cam6 /*[n_view][6]*/, int n_pair, const int32_t* h_pairs /*[n_pair][2]: (a, b)*/, int n_cand,
+                   const float* d_cand /*[n_cand] radians*/, int stride, double* d_moments /*[n_pair][n_cand][6]*/, void* d_workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* Predicted perspective fields against ground truth on the device: per-pixel errors, per-image statistics with an exact median, and
  * a running histogram for dataset statistics (field_err.hip).
  * Inputs per image: up_pred, up_gt [2][H][W] and lat_pred, lat_gt [H][W] degrees, fp32 (the layout of pred_gravity_original /

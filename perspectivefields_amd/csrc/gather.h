@@ -1,6 +1,7 @@
 // What the batched image gathers (pano_crop.hip, reproject.hip, pano_compose.hip) share on the device: the bilinear blend of four taps, the uint8 rounding rule and
 // the stores of the RGB epilogue.  Each kernel keeps its camera model and its index policy (which taps); the blend's order of operations and the
 // rounding are here alone, so that every gather gives the same bits for the same taps.  The launch's shape is GatherDims (pf_kernels.h).
+// yaw_align.hip samples one-channel fp32 planes with the same tap rule and blend order (sample_clamped_plane).
 // Two pieces stay in the kernels because no helper form of them compiled to the kernels' instructions: the four lines of
 // block -> (row, col0) arithmetic and the packing of 4 uint8 pixels into three 4-byte words.
 #pragma once
@@ -37,6 +38,19 @@ __device__ __forceinline__ void sample_clamped(const T* __restrict__ src, int Hs
   const int c0 = min(max(c, 0), Ws - 1), c1 = min(max(c + 1, 0), Ws - 1);
   const int r0 = min(max(r, 0), Hs - 1), r1 = min(max(r + 1, 0), Hs - 1);
   bilerp_rgb(src, Ws, r0, r1, c0, c1, fu, fv, out);
+}
+
+// the one-channel form: bilinear sample of an (Hs, Ws) fp32 plane at (u, v) with the tap rule and the blend order of sample_clamped
+__device__ __forceinline__ float sample_clamped_plane(const float* __restrict__ src, int Hs, int Ws, float u, float v) {
+  const float uf = floorf(u), vf = floorf(v);
+  const float fu = u - uf, fv = v - vf;
+  const int c = (int)uf, r = (int)vf;
+  const int c0 = min(max(c, 0), Ws - 1), c1 = min(max(c + 1, 0), Ws - 1);
+  const int r0 = min(max(r, 0), Hs - 1), r1 = min(max(r + 1, 0), Hs - 1);
+  const size_t o0 = (size_t)r0 * Ws, o1 = (size_t)r1 * Ws;
+  const float top = (1.f - fu) * src[o0 + c0] + fu * src[o0 + c1];
+  const float bot = (1.f - fu) * src[o1 + c0] + fu * src[o1 + c1];
+  return (1.f - fv) * top + fv * bot;
 }
 
 // uint8 of an fp32 value: rounded half up, clamped to [0, 255]

@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip), the yaw moments (yaw_align.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -167,6 +167,97 @@ int pf_pano_compose(int device, int n_view, const void* const* view, const int32
   }
   if (np > 0) launch(p0, np, v0, nv, 0u, 0u);
   if (hipGetLastError() != hipSuccess) { g_create_error = "pf_pano_compose: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+// pf_yaw_moments: workspace = every view's luminance plane, then the tiles' partial records of every pair, each region 256-byte aligned
+static constexpr int kYawMaxCand = PF_YAW_MAX_CAND;
+static size_t yaw_align(size_t n) { return (n + 255) & ~(size_t)255; }
+static long long yaw_samples(int H, int W, int stride) { return (long long)((H + stride - 1) / stride) * ((W + stride - 1) / stride); }
+// NULL, or what is wrong with the arguments that set the workspace's layout
+static const char* yaw_layout_error(int n_view, const int32_t* view_hw, int n_pair, const int32_t* pairs, int n_cand, int stride, std::string* why) {
+  if (n_view < 2 || !view_hw) return "needs at least two views (h_view, h_view_hw)";
+  if (n_pair < 1 || !pairs) return "n_pair >= 1 and h_pairs are required";
+  if (n_cand < 1 || n_cand > kYawMaxCand) { *why = fmt("n_cand %d, must be in [1, %d]", n_cand, kYawMaxCand); return why->c_str(); }
+  if (stride < 1) { *why = fmt("stride %d, must be >= 1", stride); return why->c_str(); }
+  for (int k = 0; k < n_view; ++k)
+    if (view_hw[2 * k] < 1 || view_hw[2 * k + 1] < 1 || (long long)view_hw[2 * k] * view_hw[2 * k + 1] > INT32_MAX) {
+      *why = fmt("view %d is %d x %d, smaller than 1 x 1 or of 2^31 pixels or more", k, view_hw[2 * k], view_hw[2 * k + 1]);
+      return why->c_str();
+    }
+  for (int i = 0; i < n_pair; ++i) {
+    const int a = pairs[2 * i], b = pairs[2 * i + 1];
+    if (a < 0 || a >= n_view || b < 0 || b >= n_view) { *why = fmt("pair %d: view index (%d, %d) of %d", i, a, b, n_view); return why->c_str(); }
+    if (a == b) { *why = fmt("pair %d: a == b (%d), a pair needs two views", i, a); return why->c_str(); }
+  }
+  return nullptr;
+}
+static int yaw_tiles(const int32_t* view_hw, int b, int stride) {
+  return (int)((yaw_samples(view_hw[2 * b], view_hw[2 * b + 1], stride) + YawBatch::TILE - 1) / YawBatch::TILE);
+}
+
+size_t pf_yaw_moments_workspace_bytes(int n_view, const int32_t* view_hw, int n_pair, const int32_t* pairs, int n_cand, int stride) {
+  std::string why;
+  if (yaw_layout_error(n_view, view_hw, n_pair, pairs, n_cand, stride, &why)) return 0;
+  size_t n = 256, tiles = 0;  // + 256: alignment of the caller's pointer
+  for (int k = 0; k < n_view; ++k) n += yaw_align((size_t)view_hw[2 * k] * view_hw[2 * k + 1] * sizeof(float));
+  for (int i = 0; i < n_pair; ++i) tiles += (size_t)yaw_tiles(view_hw, pairs[2 * i + 1], stride);
+  if (tiles > (size_t)INT32_MAX) return 0;
+  return n + yaw_align(tiles * n_cand * 6 * sizeof(float));
+}
+
+int pf_yaw_moments(int device, int n_view, const void* const* view, const int32_t* view_hw, int dtype, const float* d_cam6, int n_pair, const int32_t* pairs,
+                   int n_cand, const float* d_cand, int stride, double* d_moments, void* ws, size_t ws_bytes, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_yaw_moments: " + m; return PF_ERR_ARG; };
+  std::string why;
+  if (const char* e = yaw_layout_error(n_view, view_hw, n_pair, pairs, n_cand, stride, &why)) return bad(e);
+  if (!view) return bad("needs at least two views (h_view, h_view_hw)");
+  if (dtype != PF_PANO_U8 && dtype != PF_PANO_F32) return bad(fmt("unknown dtype %d", dtype));
+  for (int k = 0; k < n_view; ++k)
+    if (!view[k]) return bad(fmt("NULL pointer of view %d", k));
+  if (!d_cam6 || !d_cand || !d_moments) return bad("d_cam6, d_cand and d_moments are required");
+  if (misalign(d_moments, 15)) return bad("d_moments must be aligned to 16 bytes");
+  const size_t need = pf_yaw_moments_workspace_bytes(n_view, view_hw, n_pair, pairs, n_cand, stride);
+  if (need == 0) return bad("too many tiles: the pairs' samples / 1024 must stay below 2^31");
+  if (!ws || ws_bytes < need) return bad(fmt("needs %zu workspace bytes, got %zu", need, ws_bytes));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::vector<float*> lum(n_view);
+  for (int v0 = 0; v0 < n_view; v0 += YawLum::MAX) {
+    YawLum yl;
+    yl.n = std::min(n_view - v0, (int)YawLum::MAX);
+    yl.c = dtype == PF_PANO_U8 ? 127.5f : 0.5f;
+    for (int k = 0; k < yl.n; ++k) {
+      const int v = v0 + k;
+      yl.src.p[k] = view[v];
+      yl.src.H[k] = view_hw[2 * v]; yl.src.W[k] = view_hw[2 * v + 1];
+      yl.out[k] = lum[v] = reinterpret_cast<float*>(p);
+      p += yaw_align((size_t)view_hw[2 * v] * view_hw[2 * v + 1] * sizeof(float));
+    }
+    launch_yaw_luminance(yl, dtype, s);
+  }
+  unsigned tile0 = 0;
+  for (int i0 = 0; i0 < n_pair; i0 += YawBatch::MAX) {
+    YawBatch yb;
+    yb.n = std::min(n_pair - i0, (int)YawBatch::MAX);
+    yb.n_cand = n_cand; yb.stride = stride; yb.max_tiles = 0;
+    yb.cam = d_cam6; yb.cand = d_cand;
+    yb.part = reinterpret_cast<float*>(p);
+    yb.moments = d_moments + (size_t)i0 * n_cand * 6;
+    for (int k = 0; k < yb.n; ++k) {
+      const int a = pairs[2 * (i0 + k)], b = pairs[2 * (i0 + k) + 1];
+      const int tiles = yaw_tiles(view_hw, b, stride);
+      yb.pr[k] = YawPair{lum[a], lum[b], view_hw[2 * a], view_hw[2 * a + 1], view_hw[2 * b], view_hw[2 * b + 1], a, b, tile0, tiles};
+      yb.max_tiles = std::max(yb.max_tiles, tiles);
+      tile0 += (unsigned)tiles;
+    }
+    launch_yaw_moments(yb, s);
+    launch_yaw_sum(yb, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_yaw_moments: kernel launch failed"; return PF_ERR_DEVICE; }
   return PF_OK;
 }
 

@@ -501,6 +501,38 @@ struct ComposeBatch {
 void launch_pano_compose(const ComposeBatch& cb, int dtype, int blend, hipStream_t s);
 static_assert(offsetof(ComposeBatch, d) == 0 && offsetof(ComposeBatch, src) == 32, "ComposeBatch layout");
 
+// relative yaw of views of one centre (yaw_align.hip, include/pf_hip.h pf_yaw_moments): the luminance planes of up to YawLum::MAX views per launch, then
+// the moments of up to YawBatch::MAX ordered pairs (a, b) per launch
+struct YawLum {
+  static constexpr int MAX = GatherSources::MAX;
+  int n;              // views of this launch
+  float c;            // the constant taken off the luminance: 127.5 (uint8), 0.5 (fp32)
+  GatherSources src;  // (H, W, 3)
+  float* out[MAX];    // (H, W) fp32 planes
+};
+void launch_yaw_luminance(const YawLum& yl, int dtype, hipStream_t s);
+struct YawPair {
+  const float *La, *Lb;  // luminance planes of a (sampled) and b (whose grid gives the samples)
+  int Ha, Wa, Hb, Wb;
+  int a, b;              // rows of `cam`
+  unsigned tile0;        // the pair's first tile in `part`
+  int tiles;             // ceil(samples of b / TILE)
+};
+struct YawBatch {
+  static constexpr int MAX = 64;     // pairs per launch (the kernel arguments hold them: 48 bytes each)
+  static constexpr int TILE = 1024;  // samples of b per block, 16 bytes of LDS each
+  static constexpr int CHUNK = 64;   // candidates per block: one wavefront, one candidate per lane
+  int n, n_cand, stride, max_tiles;  // pairs of this launch; candidates; sample stride; largest `tiles` of the launch
+  const float* cam;   // [n_view][6]: roll, pitch (radians), rel_focal, rel_cx, rel_cy, xi
+  const float* cand;  // [n_cand] radians
+  float* part;        // [tile][n_cand][6] fp32: n, sum x, sum y, sum x^2, sum y^2, sum xy of one tile
+  double* moments;    // [n][n_cand][6] of this launch's pairs
+  YawPair pr[MAX];
+};
+void launch_yaw_moments(const YawBatch& yb, hipStream_t s);  // the store pass
+void launch_yaw_sum(const YawBatch& yb, hipStream_t s);      // the tiles of each (pair, candidate) added in tile order in fp64
+static_assert(sizeof(YawPair) == 48 && sizeof(YawBatch) <= 4096, "YawBatch fits the kernel arguments");
+
 // predicted fields against ground truth (field_err.hip, include/pf_hip.h pf_field_errors): up to FerrBatch::MAX images per launch,
 // per-image sizes and pointers in the kernel arguments
 constexpr int FERR_REC = 10;         // doubles of one accumulate block's partial record

@@ -550,6 +550,14 @@ class PerspectiveFields(nn.Module):
         cams["yaw"] = yaw
         return compose_panorama(images, cams, mode="deg", **kw)
 
+    def align_yaw(self, images, preds, **kw):
+        """The yaw of every image, recovered from the pictures with the cameras of `preds`, on the GPU (see align_yaw for the options -- anchor,
+        step, stride, min_overlap, min_score, refine, return_info -- and what is returned).  preds: a list of result dicts of inference* (a
+        ParamNet model) or of fit_camera, one per image, read as `rectify` reads them.  The result is what `compose_panorama` takes as `yaw`."""
+        if "mode" in kw:
+            raise ValueError("align_yaw takes the angles of its preds, which are degrees: no mode")
+        return align_yaw(images, PerspectiveFields._pred_cameras("align_yaw", preds), mode="deg", **kw)
+
     def forward(self, batched_inputs) -> List[dict]:
         """batched_inputs: list of {"image": (3,320,320) float BGR 0..255, "height", "width"} (reference :223-272)."""
         with torch.no_grad():
@@ -1389,3 +1397,191 @@ def compose_panorama(images, cams, *, height, width, pano_index=None, n_pano=Non
                                    pano.data_ptr(), weight.data_ptr() if return_weight else None, acc.data_ptr() if acc is not None else None,
                                    _stream_ptr()), None, "pf_pano_compose")
     return (pano, weight) if return_weight else pano
+
+
+_YAW_MAX_CAND = 4096   # include/pf_hip.h PF_YAW_MAX_CAND
+_YAW_CAM_COLS = (0, 1, 3, 4, 5, 6)   # _CAM_KEYS without the yaw: the row order of pf_yaw_moments's d_cam6
+
+
+def yaw_scores(images, cams, pairs, candidates, *, stride=None, min_overlap=0.1, mode="deg", return_moments=False):
+    """How well the pictures of two views of one centre agree when the second is turned by a candidate angle about the vertical against the
+    first, on the GPU.  Model: include/pf_hip.h pf_yaw_moments.
+
+    images, cams: what `compose_panorama` takes (a `yaw` entry of cams is ignored).  pairs: a sequence of (a, b) view indices, a != b.
+    candidates: the turns yaw_b - yaw_a to try, in degrees (also with mode="rad", which is about the cameras' angles), a 1-d sequence or
+    tensor of at most 4096 entries.  stride: every stride-th row and column of b is a sample; default max(1, min(H, W) // 48) of the
+    smallest view, one stride per call (a search in steps of 1 degree does not need more samples).
+    Returns (score (P, K) float64, overlap (P, K) float64) on the device; with return_moments=True also the moments (P, K, 6) float64
+    (n, sum x, sum y, sum x^2, sum y^2, sum xy of the luminances x of a and y of b over the covered samples).  score is the zero-mean
+    normalised cross-correlation, in [-1, 1], computed from the moments in float64; it is -inf where fewer than min_overlap x (samples of b
+    that have a ray) samples are covered or a variance is not positive (see _zncc).  overlap is the covered share of those samples.
+    GPU only: CPU images raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    batched = torch.is_tensor(images) and images.dim() == 4
+    srcs = [] if batched and images.shape[0] < 1 else [images] if torch.is_tensor(images) else list(images)
+    srcs, dev = _cuda_image_list("yaw_scores", srcs, ("view", "views"), "a view must be (H, W, 3) with H, W >= 1, or a tensor (B, H, W, 3)", 1,
+                                 ndim=4 if batched else 3)
+    n = int(srcs[0].shape[0]) if batched else len(srcs)
+    sizes = [(int(srcs[0].shape[1]), int(srcs[0].shape[2]))] * n if batched else [(int(p.shape[0]), int(p.shape[1])) for p in srcs]
+    if n < 2:
+        raise ValueError("yaw_scores needs at least two views")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    if stride is None:
+        stride = max(1, min(min(hw) for hw in sizes) // 48)
+    stride = operator.index(stride)
+    if stride < 1:
+        raise ValueError(f"stride must be at least 1; got {stride}")
+    min_overlap = float(min_overlap)
+    if not 0.0 <= min_overlap <= 1.0:
+        raise ValueError(f"min_overlap must be in [0, 1]; got {min_overlap}")
+    ts = _camera_params("cams", cams, "yaw_scores")
+    Bp = _broadcast_len("yaw_scores", ts)
+    if Bp not in (1, n):
+        raise ValueError(f"yaw_scores: camera parameters of length {Bp} for {n} views")
+    plist = [(operator.index(a), operator.index(b)) for a, b in (pairs.tolist() if torch.is_tensor(pairs) else pairs)]
+    if not plist:
+        raise ValueError("yaw_scores needs at least one pair")
+    for a, b in plist:
+        if not (0 <= a < n and 0 <= b < n) or a == b:
+            raise ValueError(f"a pair is two different view indices in [0, {n}); got ({a}, {b})")
+    cand = candidates if torch.is_tensor(candidates) else torch.as_tensor(np.asarray(candidates, dtype=np.float64))
+    if cand.dim() != 1 or not 1 <= cand.shape[0] <= _YAW_MAX_CAND:
+        raise ValueError(f"candidates must be a 1-d sequence of 1 to {_YAW_MAX_CAND} angles; got shape {tuple(cand.shape)}")
+    P, K = len(plist), int(cand.shape[0])
+    cam = _camera_rows(ts, (0, 1, 2), n, dev, mode)[:, list(_YAW_CAM_COLS)].contiguous()
+    cand = torch.deg2rad(cand.to(device=dev, dtype=torch.float64)).to(torch.float32).contiguous()
+    if batched:
+        whole = srcs[0].contiguous()
+        srcs = [whole[i] for i in range(n)]
+    else:
+        srcs = [p.contiguous() for p in srcs]
+    p_src, hw, _ = _source_arrays(srcs, sizes, [0])
+    c_pairs = (ctypes.c_int32 * (2 * P))(*[i for ab in plist for i in ab])
+    lib = load_library()
+    need = int(lib.pf_yaw_moments_workspace_bytes(n, hw, P, c_pairs, K, stride))
+    if need == 0:
+        raise ValueError("yaw_scores: the views, pairs and stride give more samples than one call takes")
+    moments = torch.empty((P, K, 6), dtype=torch.float64, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.pf_yaw_moments(dev.index, n, p_src, hw, _PANO_DTYPES[srcs[0].dtype], cam.data_ptr(), P, c_pairs, K, cand.data_ptr(), stride,
+                                  moments.data_ptr(), ws.data_ptr(), need, _stream_ptr()), None, "pf_yaw_moments")
+    # the samples of b that have a ray: disc >= 0 (include/pf_hip.h pf_reproject step 1), in float64 from the float32 rows the kernel reads
+    cam64, rays = cam.to(torch.float64), torch.empty(n, dtype=torch.float64, device=dev)
+    for H, W in sorted(set(sizes)):   # the views of one size together
+        own = torch.as_tensor([i for i, hw in enumerate(sizes) if hw == (H, W)], device=dev)
+        r = cam64[own]
+        x = (torch.arange(0, W, stride, device=dev, dtype=torch.float64)[None, :] + 0.5 - ((r[:, 3] + 0.5) * W)[:, None]) / (r[:, 2] * H)[:, None]
+        y = (torch.arange(0, H, stride, device=dev, dtype=torch.float64)[None, :] + 0.5 - ((r[:, 4] + 0.5) * H)[:, None]) / (r[:, 2] * H)[:, None]
+        disc = 1.0 + (1.0 - r[:, 5] * r[:, 5])[:, None, None] * (x[:, None, :] ** 2 + y[:, :, None] ** 2)
+        rays[own] = (disc >= 0).sum((1, 2)).to(torch.float64)
+    rays = rays[torch.as_tensor([b for _, b in plist], device=dev)]
+    score, overlap = _zncc(moments, rays, min_overlap)
+    return (score, overlap, moments) if return_moments else (score, overlap)
+
+
+def _zncc(moments, rays, min_overlap):
+    """moments (P, K, 6) float64 and the samples with a ray (P,) -> (score, overlap) (P, K) float64: include/pf_hip.h pf_yaw_moments's ZNCC, -inf
+    where n < min_overlap x rays or a variance is not positive (not above 2^-16 of n x its sum of squares: the sums are kept in float32 per
+    tile, which cannot tell such a variance from 0; one covered sample, or a flat picture, has no score)"""
+    n, sx, sy, sxx, syy, sxy = moments.unbind(-1)
+    va, vb = n * sxx - sx * sx, n * syy - sy * sy
+    ok = (n >= min_overlap * rays[:, None]) & (va > 2.0 ** -16 * n * sxx) & (vb > 2.0 ** -16 * n * syy)
+    one = torch.ones_like(va)
+    score = torch.where(ok, (n * sxy - sx * sy) / torch.sqrt(torch.where(ok, va, one) * torch.where(ok, vb, one)), torch.full_like(va, float("-inf")))
+    overlap = torch.where(rays[:, None] > 0, n / torch.clamp(rays[:, None], min=1.0), torch.zeros_like(n))
+    return score, overlap
+
+
+def _wrap180(x):
+    """degrees wrapped to [-180, 180)"""
+    return (x + 180.0) % 360.0 - 180.0
+
+
+def yaw_tree(delta, peak, *, anchor=0, min_score=0.8):
+    """The yaws of N views from the tables of their ordered pairs, on the host (no GPU): delta[a, b] (degrees) is the measured turn
+    yaw_b - yaw_a of the ordered pair (a, b) and peak[a, b] its score (the diagonal is ignored; -inf or NaN: no measurement).
+    Of the two orders of a pair the one with the higher peak is kept (a tie keeps a < b) and the other order's turn is its negative.  A
+    maximum spanning tree grows from `anchor` (Prim) over the pairs with a kept peak >= min_score; equal peaks go to the lower new view, then
+    to the lower parent.  The anchor's yaw is 0, a child's is its parent's plus the turn, wrapped to [-180, 180).
+    Returns (yaw (N,) float64 with NaN for the views the tree does not reach, parent (N,) int64 with -1 for the anchor and for those
+    views, linked (N,) bool)."""
+    delta, peak = np.asarray(delta, dtype=np.float64), np.asarray(peak, dtype=np.float64)
+    N = delta.shape[0]
+    if delta.shape != (N, N) or peak.shape != (N, N):
+        raise ValueError(f"delta and peak must be square tables of one size; got {delta.shape} and {peak.shape}")
+    anchor = operator.index(anchor)
+    if not 0 <= anchor < N:
+        raise ValueError(f"anchor must be in [0, {N}); got {anchor}")
+    pk = np.where(np.isfinite(peak) & np.isfinite(delta), peak, -np.inf)
+    w, turn = np.full((N, N), -np.inf), np.zeros((N, N))   # turn[u, v] = yaw_v - yaw_u of the kept order
+    for a in range(N):
+        for b in range(a + 1, N):
+            fwd = pk[a, b] >= pk[b, a]
+            w[a, b] = w[b, a] = pk[a, b] if fwd else pk[b, a]
+            turn[a, b] = delta[a, b] if fwd else -delta[b, a]
+            turn[b, a] = -turn[a, b]
+    yaw, parent, linked = np.full(N, np.nan), np.full(N, -1, dtype=np.int64), np.zeros(N, dtype=bool)
+    yaw[anchor], linked[anchor] = 0.0, True
+    while True:
+        best = None
+        for v in range(N):
+            if linked[v]:
+                continue
+            for u in range(N):
+                if linked[u] and w[u, v] >= min_score and (best is None or w[u, v] > best[0]):
+                    best = (w[u, v], v, u)
+        if best is None:
+            return yaw, parent, linked
+        _, v, u = best
+        yaw[v], parent[v], linked[v] = _wrap180(yaw[u] + turn[u, v]), u, True
+
+
+def align_yaw(images, cams, *, anchor=0, step=1.0, stride=None, min_overlap=0.1, min_score=0.8, refine=True, mode="deg", return_info=False):
+    """The yaw of every view of one centre, recovered from the pictures on the GPU: the one camera parameter the perspective fields do not
+    carry, and what `compose_panorama` takes as `yaw`.  Model: include/pf_hip.h pf_yaw_moments.
+
+    images, cams: what `compose_panorama` takes, N >= 2 views with their roll, pitch and intrinsics (a `yaw` entry is ignored).  Every ordered
+    pair (a, b), a != b, is scored by `yaw_scores` (see there for stride and min_overlap) at the candidates -180 + k step, k < round(360 / step)
+    degrees; its turn is the candidate with the highest score, with refine=True moved by the vertex of the parabola through that score and its
+    two circular neighbours (not moved where a neighbour has no score).  `yaw_tree` then places the views: a maximum spanning tree from
+    `anchor` over the pairs whose score reaches min_score.
+    Returns yaw (N,) float64 in degrees on the device, in [-180, 180), 0 for the anchor and NaN for a view that no pair of sufficient score
+    ties to the anchor's tree.  With return_info=True also a dict: `delta`, `peak`, `overlap` (N, N) float64 on the device, by ordered pair
+    [a, b] (NaN, -inf, 0 on the diagonal), and `parent` (N,) int64, `linked` (N,) bool on the host.
+    min_score = 0.8 lies between the scores of overlapping views of one scene (0.98 and more on the low-pass test scenes) and of views
+    that do not overlap or show different scenes (0.58 and less there).  It is a default, not a guarantee: repetitive scenes can score
+    high at a wrong turn, and strongly differing exposure, parallax or moving objects lower the score of a right one.
+    GPU only: CPU images raise PfError."""
+    step = float(step)
+    if not (step > 0 and round(360.0 / step) >= 1 and round(360.0 / step) <= _YAW_MAX_CAND):
+        raise ValueError(f"step must give 1 to {_YAW_MAX_CAND} candidates (360 / step); got {step}")
+    min_score = float(min_score)
+    n = int(images.shape[0]) if torch.is_tensor(images) and images.dim() == 4 else 1 if torch.is_tensor(images) else len(images)
+    if n >= 2 and not 0 <= operator.index(anchor) < n:
+        raise ValueError(f"anchor must be in [0, {n}); got {anchor}")
+    K = int(round(360.0 / step))
+    cand = -180.0 + step * np.arange(K, dtype=np.float64)
+    pairs = [(a, b) for a in range(n) for b in range(n) if a != b]
+    score, overlap = yaw_scores(images, cams, pairs, cand, stride=stride, min_overlap=min_overlap, mode=mode)
+    dev = score.device
+    peak, k = score.max(dim=1)
+    delta = torch.as_tensor(cand, device=dev)[k]
+    if refine and K >= 3:
+        zm, zp = score.gather(1, ((k - 1) % K)[:, None])[:, 0], score.gather(1, ((k + 1) % K)[:, None])[:, 0]
+        curv = zm - 2.0 * peak + zp
+        ok = torch.isfinite(zm) & torch.isfinite(zp) & torch.isfinite(peak) & (curv < 0)
+        delta = delta + step * torch.where(ok, 0.5 * (zm - zp) / torch.where(ok, curv, torch.ones_like(curv)), torch.zeros_like(curv))
+    idx = torch.as_tensor(pairs, device=dev)
+    tables = torch.zeros((3, n, n), dtype=torch.float64, device=dev)
+    tables[0].fill_(float("nan"))
+    tables[1].fill_(float("-inf"))
+    tables[:, idx[:, 0], idx[:, 1]] = torch.stack([delta, peak, overlap.gather(1, k[:, None])[:, 0]])
+    host = tables[:2].cpu().numpy()   # the one copy to the host
+    yaw, parent, linked = yaw_tree(host[0], host[1], anchor=anchor, min_score=min_score)
+    yaw = torch.as_tensor(yaw, device=dev)
+    if return_info:
+        return yaw, dict(delta=tables[0], peak=tables[1], overlap=tables[2], parent=parent, linked=linked)
+    return yaw
