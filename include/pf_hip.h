@@ -523,6 +523,38 @@ int pf_yaw_moments(int device, int n_view, const void* const* h_view, const int3
                    const float* d_cand /*[n_cand] radians*/, int stride, double* d_moments /*[n_pair][n_cand][6]*/, void* d_workspace,
                    size_t workspace_bytes, void* stream);
 
+/* Perspective-aware compositing: the Perspective Field Discrepancy of an object's fields against a background's at every place the object could be
+ * pasted (place_score.hip).
+ * Inputs: background up_bg [2][H][W] and lat_bg [H][W], object up_obj [2][h][w] and lat_obj [h][w], degrees, fp32 (the layout of
+ * pred_gravity_original / pred_latitude_original and of pf_pano_crop's labels), 1 <= h <= H, 1 <= w <= W.
+ * A field pixel is VALID when its three values are finite and the fp32 squared length of its up vector, fmaf(u_x, u_x, u_y u_y), is >= 1e-12 and
+ * finite: pf_field_errors' rule, applied to each field on its own.  A caller masks a pixel by writing NaN into its latitude, so a silhouette is
+ * NaN outside the object, and a background padded with NaN lets the object hang over the border.
+ * Placements: (j, i) with 0 <= j < P = (H - h) / stride + 1 and 0 <= i < Q = (W - w) / stride + 1 (integer divisions); the object's pixel (r, c)
+ * lies on the background's (j stride + r, i stride + c); the object is always fully inside the array.
+ * Per pixel pair whose two pixels are valid:
+ *   e_up   the angle between the two up vectors in degrees, in [0, 180]: mathematically pf_field_errors' atan2(|cross|, dot), computed as
+ *          min(d, 360 - d) with d = |theta_bg - theta_obj| and theta = atan2f(u_y, u_x) in fp32 degrees, clamped to [-180, 180], taken once per
+ *          pixel and not once per pair.  Equal vectors give exactly 0; two vectors on either side of +-180 give their small angle
+ *   e_lat  |lat_bg - lat_obj|
+ * Per placement n = the number of valid pairs, S_up = sum e_up, S_lat = sum e_lat over them:
+ *   d_out[pair][j][i] = {S_up, S_lat, n} as fp64, the pairs one after the other, P Q 3 doubles each: fp32 sums over chunks of 1024 object pixels in
+ *   row-major order, the chunks added in order in fp64.
+ * The caller's scores are the means S_up / n and S_lat / n and their weighted sum, the paper's PFD at weights (1, 1).
+ * Every value depends on its pair's two fields and the stride only: the same bits in any batch of pairs and on every run.
+ * h_bg_up, h_bg_lat = HOST arrays of n_bg (>= 1) DEVICE pointers; h_bg_hw = HOST [n_bg][2] (H, W), each >= 1, H W < 2^31; h_obj_* likewise for the
+ * n_obj (>= 1) objects; h_pairs = HOST [n_pair][2] (background, object) indices; stride >= 1, one per call; d_out 8-byte aligned; workspace of
+ * pf_place_scores_workspace_bytes (0 for arguments pf_place_scores rejects): a packed plane per field, written once per call, and the chunks' records.
+ * Argument errors (counts < 1, NULL pointers, a side < 1, a pair index out of range, an object larger than its background or of more than 65535
+ * chunks, stride < 1, a small workspace, a misaligned d_out) return PF_ERR_ARG before any device work.  One pack launch per 32 fields, a store
+ * launch and a sum launch per 32 pairs, all on `stream`, no atomics, no host-to-device copy, no host synchronisation; stateless, no handle. */
+size_t pf_place_scores_workspace_bytes(int n_bg, const int32_t* h_bg_hw /*[n_bg][2]*/, int n_obj, const int32_t* h_obj_hw /*[n_obj][2]*/, int n_pair,
+                                       const int32_t* h_pairs /*[n_pair][2]*/, int stride);
+int pf_place_scores(int device, int n_bg, const float* const* h_bg_up, const float* const* h_bg_lat, const int32_t* h_bg_hw /*[n_bg][2]*/, int n_obj,
+                    const float* const* h_obj_up, const float* const* h_obj_lat, const int32_t* h_obj_hw /*[n_obj][2]*/, int n_pair,
+                    const int32_t* h_pairs /*[n_pair][2]: (background, object)*/, int stride, double* d_out /*[pair][P][Q][3]*/, void* d_workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* Predicted perspective fields against ground truth on the device: per-pixel errors, per-image statistics with an exact median, and
  * a running histogram for dataset statistics (field_err.hip).
  * Inputs per image: up_pred, up_gt [2][H][W] and lat_pred, lat_gt [H][W] degrees, fp32 (the layout of pred_gravity_original /

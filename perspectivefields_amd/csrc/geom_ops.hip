@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip), the yaw moments (yaw_align.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -258,6 +258,119 @@ int pf_yaw_moments(int device, int n_view, const void* const* view, const int32_
     launch_yaw_sum(yb, s);
   }
   if (hipGetLastError() != hipSuccess) { g_create_error = "pf_yaw_moments: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+// pf_place_scores: workspace = every field's packed plane (backgrounds, then objects), then the chunks' partial records of every pair, each region
+// 256-byte aligned
+struct PlaceDims { int P, Q, chunks; };
+// NULL, or what is wrong with the arguments that set the workspace's layout
+static const char* place_layout_error(int n_bg, const int32_t* bg_hw, int n_obj, const int32_t* obj_hw, int n_pair, const int32_t* pairs, int stride,
+                                      std::string* why) {
+  if (n_bg < 1 || !bg_hw) return "n_bg >= 1 and h_bg_hw are required";
+  if (n_obj < 1 || !obj_hw) return "n_obj >= 1 and h_obj_hw are required";
+  if (n_pair < 1 || !pairs) return "n_pair >= 1 and h_pairs are required";
+  if (stride < 1) { *why = fmt("stride %d, must be >= 1", stride); return why->c_str(); }
+  for (int f = 0; f < n_bg + n_obj; ++f) {
+    const int32_t* hw = f < n_bg ? bg_hw + 2 * f : obj_hw + 2 * (f - n_bg);
+    if (hw[0] < 1 || hw[1] < 1 || (long long)hw[0] * hw[1] > INT32_MAX) {
+      *why = fmt("%s %d is %d x %d, smaller than 1 x 1 or of 2^31 pixels or more", f < n_bg ? "background" : "object", f < n_bg ? f : f - n_bg, hw[0], hw[1]);
+      return why->c_str();
+    }
+  }
+  for (int k = 0; k < n_pair; ++k) {
+    const int b = pairs[2 * k], o = pairs[2 * k + 1];
+    if (b < 0 || b >= n_bg || o < 0 || o >= n_obj) {
+      *why = fmt("pair %d: index (%d, %d) of (%d backgrounds, %d objects)", k, b, o, n_bg, n_obj);
+      return why->c_str();
+    }
+    if (obj_hw[2 * o] > bg_hw[2 * b] || obj_hw[2 * o + 1] > bg_hw[2 * b + 1]) {
+      *why = fmt("pair %d: the object (%d x %d) is larger than its background (%d x %d)", k, obj_hw[2 * o], obj_hw[2 * o + 1], bg_hw[2 * b], bg_hw[2 * b + 1]);
+      return why->c_str();
+    }
+    if (((long long)obj_hw[2 * o] * obj_hw[2 * o + 1] + PlaceBatch::CHUNK - 1) / PlaceBatch::CHUNK > 65535) {
+      *why = fmt("pair %d: the object (%d x %d) has more than 65535 chunks of %d pixels", k, obj_hw[2 * o], obj_hw[2 * o + 1], (int)PlaceBatch::CHUNK);
+      return why->c_str();
+    }
+  }
+  return nullptr;
+}
+static PlaceDims place_dims(const int32_t* bg_hw, const int32_t* obj_hw, const int32_t* pair, int stride) {
+  const int32_t *b = bg_hw + 2 * pair[0], *o = obj_hw + 2 * pair[1];
+  return PlaceDims{(b[0] - o[0]) / stride + 1, (b[1] - o[1]) / stride + 1, (int)(((long long)o[0] * o[1] + PlaceBatch::CHUNK - 1) / PlaceBatch::CHUNK)};
+}
+static size_t place_plane_bytes(const int32_t* hw) { return yaw_align((size_t)hw[0] * hw[1] * sizeof(float2)); }
+
+size_t pf_place_scores_workspace_bytes(int n_bg, const int32_t* bg_hw, int n_obj, const int32_t* obj_hw, int n_pair, const int32_t* pairs, int stride) {
+  std::string why;
+  if (place_layout_error(n_bg, bg_hw, n_obj, obj_hw, n_pair, pairs, stride, &why)) return 0;
+  size_t n = 256, rec = 0;  // + 256: alignment of the caller's pointer
+  for (int f = 0; f < n_bg; ++f) n += place_plane_bytes(bg_hw + 2 * f);
+  for (int f = 0; f < n_obj; ++f) n += place_plane_bytes(obj_hw + 2 * f);
+  for (int k = 0; k < n_pair; ++k) {
+    const PlaceDims d = place_dims(bg_hw, obj_hw, pairs + 2 * k, stride);
+    rec += (size_t)d.P * d.Q * d.chunks;
+  }
+  return n + yaw_align(rec * 3 * sizeof(float));
+}
+
+int pf_place_scores(int device, int n_bg, const float* const* bg_up, const float* const* bg_lat, const int32_t* bg_hw, int n_obj, const float* const* obj_up,
+                    const float* const* obj_lat, const int32_t* obj_hw, int n_pair, const int32_t* pairs, int stride, double* d_out, void* ws, size_t ws_bytes,
+                    void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_place_scores: " + m; return PF_ERR_ARG; };
+  std::string why;
+  if (const char* e = place_layout_error(n_bg, bg_hw, n_obj, obj_hw, n_pair, pairs, stride, &why)) return bad(e);
+  if (!bg_up || !bg_lat || !obj_up || !obj_lat || !d_out) return bad("h_bg_up, h_bg_lat, h_obj_up, h_obj_lat and d_out are required");
+  for (int f = 0; f < n_bg; ++f)
+    if (!bg_up[f] || !bg_lat[f]) return bad(fmt("NULL field pointer of background %d", f));
+  for (int f = 0; f < n_obj; ++f)
+    if (!obj_up[f] || !obj_lat[f]) return bad(fmt("NULL field pointer of object %d", f));
+  if (misalign(d_out, 7)) return bad("d_out must be aligned to 8 bytes");
+  const size_t need = pf_place_scores_workspace_bytes(n_bg, bg_hw, n_obj, obj_hw, n_pair, pairs, stride);
+  if (!ws || ws_bytes < need) return bad(fmt("needs %zu workspace bytes, got %zu", need, ws_bytes));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int n_field = n_bg + n_obj;
+  std::vector<float2*> plane(n_field);  // backgrounds, then objects
+  for (int f0 = 0; f0 < n_field; f0 += PlacePack::MAX) {
+    PlacePack pp;
+    pp.n = std::min(n_field - f0, (int)PlacePack::MAX);
+    for (int k = 0; k < pp.n; ++k) {
+      const int f = f0 + k;
+      const int32_t* hw = f < n_bg ? bg_hw + 2 * f : obj_hw + 2 * (f - n_bg);
+      pp.npx[k] = hw[0] * hw[1];
+      pp.up[k] = f < n_bg ? bg_up[f] : obj_up[f - n_bg];
+      pp.lat[k] = f < n_bg ? bg_lat[f] : obj_lat[f - n_bg];
+      pp.out[k] = plane[f] = reinterpret_cast<float2*>(p);
+      p += place_plane_bytes(hw);
+    }
+    launch_place_pack(pp, s);
+  }
+  size_t part0 = 0, out0 = 0;
+  for (int i0 = 0; i0 < n_pair; i0 += PlaceBatch::MAX) {
+    PlaceBatch pb;
+    pb.n = std::min(n_pair - i0, (int)PlaceBatch::MAX);
+    pb.stride = stride; pb.max_tiles = 0; pb.max_chunks = 0;
+    pb.part = reinterpret_cast<float*>(p);
+    pb.out = d_out;
+    for (int k = 0; k < pb.n; ++k) {
+      const int32_t* pair = pairs + 2 * (i0 + k);
+      const PlaceDims d = place_dims(bg_hw, obj_hw, pair, stride);
+      const int np = d.P * d.Q;  // <= the background's pixels < 2^31
+      pb.pr[k] = PlacePair{plane[pair[0]], plane[n_bg + pair[1]], bg_hw[2 * pair[0] + 1], obj_hw[2 * pair[1] + 1], obj_hw[2 * pair[1]] * obj_hw[2 * pair[1] + 1],
+                           d.Q, np, d.chunks, part0, out0};
+      pb.max_tiles = std::max(pb.max_tiles, (int)(((long long)np + PlaceBatch::TILE - 1) / PlaceBatch::TILE));
+      pb.max_chunks = std::max(pb.max_chunks, d.chunks);
+      part0 += (size_t)np * d.chunks;
+      out0 += (size_t)np;
+    }
+    launch_place_score(pb, s);
+    launch_place_sum(pb, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_place_scores: kernel launch failed"; return PF_ERR_DEVICE; }
   return PF_OK;
 }
 

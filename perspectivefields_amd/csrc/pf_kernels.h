@@ -533,6 +533,40 @@ void launch_yaw_moments(const YawBatch& yb, hipStream_t s);  // the store pass
 void launch_yaw_sum(const YawBatch& yb, hipStream_t s);      // the tiles of each (pair, candidate) added in tile order in fp64
 static_assert(sizeof(YawPair) == 48 && sizeof(YawBatch) <= 4096, "YawBatch fits the kernel arguments");
 
+// placement scores of an object's fields on a background's (place_score.hip, include/pf_hip.h pf_place_scores): the packed (theta, latitude) planes of
+// up to PlacePack::MAX fields per launch, then the sums of up to PlaceBatch::MAX (background, object) pairs per launch
+struct PlacePack {
+  static constexpr int MAX = 32;
+  int n;                  // fields of this launch
+  int npx[MAX];           // H * W
+  const float* up[MAX];   // (2, H, W) degrees
+  const float* lat[MAX];  // (H, W) degrees
+  float2* out[MAX];       // (H, W) records (theta = atan2(u_y, u_x) in degrees, latitude), both NaN where the pixel is invalid
+};
+void launch_place_pack(const PlacePack& pp, hipStream_t s);
+struct PlacePair {
+  const float2 *bg, *obj;  // packed planes
+  int W, w;                // row lengths of the background and of the object
+  int obj_px;              // h * w
+  int Q;                   // placements across
+  int np;                  // P * Q placements
+  int chunks;              // ceil(obj_px / CHUNK)
+  size_t part0;            // the pair's first record in `part`; chunk c's records follow at part0 + c * np
+  size_t out0;             // the pair's first record in `out`
+};
+struct PlaceBatch {
+  static constexpr int MAX = 32;      // pairs per launch (the kernel arguments hold them: 56 bytes each)
+  static constexpr int TILE = 256;    // placements per block, in row-major order: one per thread
+  static constexpr int CHUNK = 1024;  // object pixels per block, in row-major order: the terms one thread adds in fp32
+  int n, stride, max_tiles, max_chunks;  // pairs of this launch; placement stride; largest ceil(np / TILE) and `chunks` of the launch
+  float* part;    // [record][3] fp32: S_up, S_lat, n of one (placement, chunk)
+  double* out;    // [record][3]
+  PlacePair pr[MAX];
+};
+void launch_place_score(const PlaceBatch& pb, hipStream_t s);  // the store pass
+void launch_place_sum(const PlaceBatch& pb, hipStream_t s);    // the chunks of each placement added in chunk order in fp64
+static_assert(sizeof(PlacePair) == 56 && sizeof(PlaceBatch) <= 4096 && sizeof(PlacePack) <= 4096, "PlaceBatch and PlacePack fit the kernel arguments");
+
 // predicted fields against ground truth (field_err.hip, include/pf_hip.h pf_field_errors): up to FerrBatch::MAX images per launch,
 // per-image sizes and pointers in the kernel arguments
 constexpr int FERR_REC = 10;         // doubles of one accumulate block's partial record

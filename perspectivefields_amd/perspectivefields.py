@@ -498,6 +498,18 @@ class PerspectiveFields(nn.Module):
         ups, lats = [p["pred_gravity_original"] for p in plist], [p["pred_latitude_original"] for p in plist]
         return field_errors(ups[0], lats[0], up_gt, lat_gt, **kw) if single else field_errors(ups, lats, up_gt, lat_gt, **kw)
 
+    def placement_scores(self, pred_bg, pred_obj, **kw):
+        """The Perspective Field Discrepancy of pasting the picture of `pred_obj` onto the picture of `pred_bg` at every offset, on the GPU, from
+        the dense fields of inference* results: one result dict each, or lists of them (every background against every object unless `pairs` says
+        otherwise); see placement_scores for the options -- mask, stride, pairs, min_valid, weights -- and the returned entries."""
+        def fields(preds):
+            single = isinstance(preds, dict)
+            plist = [preds] if single else list(preds)
+            ups, lats = [p["pred_gravity_original"] for p in plist], [p["pred_latitude_original"] for p in plist]
+            return (ups[0], lats[0]) if single else (ups, lats)
+
+        return placement_scores(*fields(pred_bg), *fields(pred_obj), **kw)
+
     @staticmethod
     def _pred_cameras(fn, preds):
         """the cameras of inference* / fit_camera results as a dict of one column per parameter (degrees), on the device where the results hold tensors"""
@@ -950,21 +962,21 @@ _FERR_BINS, _FERR_BINS_PER_DEG = 11520, 64
 _FERR_SUMS = ("n", "sum", "sum_sq", "max", "below")
 
 
-def _field_list(what, up, lat):
+def _field_list(what, up, lat, fn="field_errors"):
     """one (2,H,W) / (H,W) pair, a batched (B,2,H,W) / (B,H,W) pair or lists of pairs -> (is a single pair, [up], [lat])"""
     if torch.is_tensor(up) != torch.is_tensor(lat):
-        raise TypeError(f"field_errors: {what} up field and latitude must both be tensors or both be lists")
+        raise TypeError(f"{fn}: {what} up field and latitude must both be tensors or both be lists")
     if torch.is_tensor(up):
         if up.dim() == 4 and lat.dim() == 3:
             if up.shape[0] != lat.shape[0]:
-                raise ValueError(f"field_errors: {what} up {tuple(up.shape)} and latitude {tuple(lat.shape)} differ in batch size")
+                raise ValueError(f"{fn}: {what} up {tuple(up.shape)} and latitude {tuple(lat.shape)} differ in batch size")
             return False, list(up.unbind(0)), list(lat.unbind(0))
         return True, [up], [lat]
     if not isinstance(up, (list, tuple)) or not isinstance(lat, (list, tuple)):
-        raise TypeError("field_errors takes torch tensors or lists of them")
+        raise TypeError(f"{fn} takes torch tensors or lists of them")
     ups, lats = list(up), list(lat)
     if len(ups) != len(lats):
-        raise ValueError(f"field_errors: {len(ups)} {what} up fields for {len(lats)} latitude maps")
+        raise ValueError(f"{fn}: {len(ups)} {what} up fields for {len(lats)} latitude maps")
     return False, ups, lats
 
 
@@ -1035,6 +1047,114 @@ def field_errors(up_pred, lat_pred, up_gt, lat_gt, *, threshold_deg=5.0, return_
     error map.  No valid pixel: NaN statistics and valid_pixels = 0.  Deterministic; an image's numbers do not depend on the batch
     it is in.  GPU only: CPU tensors raise PfError."""
     return _field_errors(up_pred, lat_pred, up_gt, lat_gt, threshold_deg, return_maps)
+
+
+def placement_scores(up_bg, lat_bg, up_obj, lat_obj, *, mask=None, stride=1, pairs=None, min_valid=0.5, weights=(1.0, 1.0)):
+    """Perspective-aware compositing on the GPU: the Perspective Field Discrepancy (PFD) of an object cut from one picture against a background
+    at every place it could be pasted -- the mean up-vector angle plus the mean latitude difference over the object's pixels; a low PFD is what
+    people judge as "fits".  Definitions: include/pf_hip.h pf_place_scores.
+
+    up_bg (2,H,W), lat_bg (H,W) and up_obj (2,h,w), lat_obj (h,w) in degrees with h <= H, w <= W (the layout of `pred_gravity_original` /
+    `pred_latitude_original` and of crop_panorama's labels): one set of device tensors each, batched tensors, or lists (sizes may differ).  A
+    pixel with a non-finite value or an up vector shorter than 1e-6 is invalid in its own field, and a pixel pair counts only where both are
+    valid: a NaN latitude masks a pixel, a silhouette is NaN outside the object, a background padded with NaN lets the object hang over the
+    border.  mask: a bool (h,w) tensor, or a list of one per object (None entries allowed), True on the object; applied as NaN on a copy of
+    the object's latitude.  The placement (j, i) puts the object's corner on background pixel (j stride, i stride); there are
+    P x Q = ((H - h) // stride + 1) x ((W - w) // stride + 1) of them.  pairs: (background, object) index pairs, default every combination,
+    backgrounds outermost.
+    Returns one dict per pair (a single dict when both sides are a single set) of device tensors, no host synchronisation:
+    up_mean_deg, lat_mean_deg (P,Q) float64, the means over the valid pairs (NaN where there is none); pfd_deg (P,Q) float64 =
+    weights[0] up_mean_deg + weights[1] lat_mean_deg, the paper's sum at the default (1, 1), +inf where fewer than min_valid x (valid pixels of
+    the object) pairs are valid or the object has no valid pixel; valid_pixels (P,Q) int64; best_offset (2,) int64, (row, col) of the lowest
+    PFD in background pixels, the first in row-major order, (-1, -1) when every placement is +inf; best_pfd_deg; stride.
+    The fields of a resized crop are the resized fields, so scale is the caller's: resize the object's fields and call again.  A search over
+    scales or rotations is out of scope.  Deterministic; a pair's numbers do not depend on the other pairs.  GPU only: CPU tensors raise
+    PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    fn = "placement_scores"
+    s_b, ups_b, lats_b = _field_list("background", up_bg, lat_bg, fn)
+    s_o, ups_o, lats_o = _field_list("object", up_obj, lat_obj, fn)
+    if not ups_b or not ups_o:
+        raise ValueError(f"{fn} needs at least one background and one object")
+    every = ups_b + lats_b + ups_o + lats_o
+    if not all(torch.is_tensor(t) for t in every):
+        raise TypeError(f"{fn} takes torch tensors")
+    for u, l in zip(ups_b + ups_o, lats_b + lats_o):
+        if u.dim() != 3 or u.shape[0] != 2 or min(u.shape[1:]) < 1 or tuple(l.shape) != tuple(u.shape[1:]):
+            raise ValueError(f"up must be (2, H, W) and lat (H, W) with H, W >= 1; got {tuple(u.shape)} and {tuple(l.shape)}")
+    stride = operator.index(stride)
+    if stride < 1:
+        raise ValueError(f"stride must be at least 1; got {stride}")
+    min_valid = float(min_valid)
+    if not 0.0 <= min_valid <= 1.0:
+        raise ValueError(f"min_valid must be in [0, 1]; got {min_valid}")
+    w_up, w_lat = (float(v) for v in weights)
+    if not (w_up >= 0.0 and w_lat >= 0.0 and np.isfinite(w_up) and np.isfinite(w_lat)):
+        raise ValueError(f"weights must be two finite numbers >= 0; got {weights}")
+    nb, no = len(ups_b), len(ups_o)
+    if pairs is None:
+        plist = [(b, o) for b in range(nb) for o in range(no)]
+    else:
+        plist = [(operator.index(b), operator.index(o)) for b, o in (pairs.tolist() if torch.is_tensor(pairs) else pairs)]
+        if not plist:
+            raise ValueError(f"{fn} needs at least one pair")
+    single = s_b and s_o and len(plist) == 1
+    for b, o in plist:
+        if not (0 <= b < nb and 0 <= o < no):
+            raise ValueError(f"a pair is (background, object) with indices in [0, {nb}) and [0, {no}); got ({b}, {o})")
+        if ups_o[o].shape[1] > ups_b[b].shape[1] or ups_o[o].shape[2] > ups_b[b].shape[2]:
+            raise ValueError(f"the object {tuple(ups_o[o].shape[1:])} is larger than its background {tuple(ups_b[b].shape[1:])}")
+    masks = [None] * no if mask is None else [mask] if torch.is_tensor(mask) else list(mask)
+    if len(masks) != no:
+        raise ValueError(f"{len(masks)} masks for {no} objects")
+    for m, l in zip(masks, lats_o):
+        if m is not None and (not torch.is_tensor(m) or m.dtype != torch.bool or tuple(m.shape) != tuple(l.shape)):
+            raise ValueError(f"a mask is a bool tensor of its object's size {tuple(l.shape)}")
+    every += [m for m in masks if m is not None]
+    if not all(t.is_cuda for t in every):
+        raise PfError(f"{fn} runs on the GPU only (no CPU path)")
+    dev = every[0].device
+    if any(t.device != dev for t in every):
+        raise ValueError(f"{fn}: all fields and masks must be on one device")
+    ups_b, lats_b, ups_o, lats_o = ([t.to(torch.float32).contiguous() for t in ts] for ts in (ups_b, lats_b, ups_o, lats_o))
+    lats_o = [l if m is None else torch.where(m, l, torch.full_like(l, float("nan"))) for l, m in zip(lats_o, masks)]
+    ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    sizes = lambda ts: (ctypes.c_int32 * (2 * len(ts)))(*[s for u in ts for s in (int(u.shape[1]), int(u.shape[2]))])
+    hw_b, hw_o = sizes(ups_b), sizes(ups_o)
+    n_pair = len(plist)
+    c_pairs = (ctypes.c_int32 * (2 * n_pair))(*[i for bo in plist for i in bo])
+    dims = [((ups_b[b].shape[1] - ups_o[o].shape[1]) // stride + 1, (ups_b[b].shape[2] - ups_o[o].shape[2]) // stride + 1) for b, o in plist]
+    lib = load_library()
+    need = int(lib.pf_place_scores_workspace_bytes(nb, hw_b, no, hw_o, n_pair, c_pairs, stride))
+    if need == 0:
+        raise ValueError(f"{fn}: field sizes that one call does not take (2^31 pixels or more, or an object of more than 65535 x 1024 pixels)")
+    out = torch.empty(3 * sum(P * Q for P, Q in dims), dtype=torch.float64, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.pf_place_scores(dev.index, nb, ptrs(ups_b), ptrs(lats_b), hw_b, no, ptrs(ups_o), ptrs(lats_o), hw_o, n_pair, c_pairs, stride,
+                                   out.data_ptr(), ws.data_ptr(), need, _stream_ptr()), None, "pf_place_scores")
+    # the valid pixels of every object, by the kernel's rule in float32 (a * a + b * b rounds twice where the kernel's fmaf rounds once: the two can
+    # differ only for a squared length within an ulp of 1e-12)
+    obj_valid = []
+    for u, l in zip(ups_o, lats_o):
+        l2 = u[0] * u[0] + u[1] * u[1]
+        obj_valid.append((torch.isfinite(l) & (l2 >= 1e-12) & torch.isfinite(l2)).sum().to(torch.float64))
+    inf = torch.tensor(float("inf"), dtype=torch.float64, device=dev)
+    res, first = [], 0
+    for (b, o), (P, Q) in zip(plist, dims):
+        rec = out[first:first + 3 * P * Q].view(P, Q, 3)
+        first += 3 * P * Q
+        n = rec[..., 2]
+        up_mean, lat_mean = rec[..., 0] / n, rec[..., 1] / n   # NaN where n = 0
+        ok = (n >= min_valid * obj_valid[o]) & (n > 0)
+        pfd = torch.where(ok, w_up * up_mean + w_lat * lat_mean, inf)
+        best = pfd.min()
+        flat = torch.where(pfd.reshape(-1) == best, torch.arange(P * Q, device=dev), P * Q).min()   # the first of equal minima
+        at = torch.stack([torch.div(flat, Q, rounding_mode="floor"), flat % Q]) * stride
+        res.append(dict(pfd_deg=pfd, up_mean_deg=up_mean, lat_mean_deg=lat_mean, valid_pixels=n.to(torch.int64),
+                        best_offset=torch.where(torch.isfinite(best), at, torch.full_like(at, -1)), best_pfd_deg=best, stride=stride))
+    return res[0] if single else res
 
 
 class FieldErrorAccumulator:
