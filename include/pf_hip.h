@@ -555,6 +555,53 @@ int pf_place_scores(int device, int n_bg, const float* const* h_bg_up, const flo
                     const int32_t* h_pairs /*[n_pair][2]: (background, object)*/, int stride, double* d_out /*[pair][P][Q][3]*/, void* d_workspace,
                     size_t workspace_bytes, void* stream);
 
+/* Perspective fields drawn over their images on the device: a latitude tint, iso-latitude lines and up arrows (draw_fields.hip, DESIGN.md
+ * section 22).  The drawing model is this library's own; parity with a plotting library's rasteriser is not offered.
+ * Per image: the picture img [H][W][3] (channel-interleaved, uint8 or fp32, values on the 0 - 255 scale in both types: the colours below are given on
+ * it), up [2][H][W] and lat [H][W] degrees, fp32 (the layout of pred_gravity_original / pred_latitude_original), all of the image's size; out of
+ * the picture's type and shape, which may be the picture itself.
+ * A pixel is VALID when its three field values are finite and the fp32 squared length of its up vector, fmaf(u_x, u_x, u_y u_y), is >= 1e-12 and
+ * finite: the rule of pf_field_errors, so NaN is the mask.  A latitude is FINITE when it is neither NaN nor infinite.
+ * Output pixel (row, col) has the centre p = (col + 1/2, row + 1/2).  v = the fp32 value of the input pixel, per channel; three layers are put
+ * "over" it in this order:
+ *   1 tint    (PF_DRAW_LAT)  valid pixels only: c = ramp(lat), the piecewise-linear map through PF_DRAW_RAMP at -90, -45, 0, 45, 90 degrees:
+ *             t = clamp((lat + 90) / 45, 0, 4), i = min(floor(t), 3), c = (1 - (t - i)) RAMP[i] + (t - i) RAMP[i + 1];  v <- (1 - alpha) v + alpha c
+ *   2 lines   (PF_DRAW_LAT)  g = (g_x, g_y), the gradient of lat in degrees per pixel: per component the central difference (next - previous) / 2
+ *             where both neighbours are inside the image and finite, else the one-sided difference with the one that is, else 0.
+ *             k = lat_step_deg rint(lat / lat_step_deg), ties to even; d = |lat - k| / |g|; w' = line_width, 2 line_width for k = 0 (the horizon);
+ *             cov = clamp(1/2 + w' / 2 - d, 0, 1), 0 where the pixel is not valid or not |g| >= PF_DRAW_GRAD_FLOOR;
+ *             v <- (1 - cov) v + cov PF_DRAW_LINE_RGB
+ *   3 arrows  (PF_DRAW_UP)   anchors: the pixels (j s + s / 2, i s + s / 2) inside the image, s = spacing, integer divisions; a = the pixel's centre.
+ *             A valid anchor pixel carries an arrow: u = its up vector times 1 / sqrt(its squared length) (x right, y down: an upright camera's
+ *             arrows point to the top of the picture), L = arrow_len_rel W (the fp32 product), three segments given by a start, a unit
+ *             direction and a length: the shaft (a, u, L) and two barbs (a + L u, R(+-PF_DRAW_HEAD_ANGLE) (-u), PF_DRAW_HEAD_RATIO L) with
+ *             R(t) (x, y) = (x cos t - y sin t, x sin t + y cos t).  dist(p, (b, e, l)) = |r - clamp(r . e, 0, l) e| with r = p - b.
+ *             cov = the maximum over all arrows and their segments of clamp(1/2 + line_width / 2 - dist, 0, 1), a maximum and not a sum: the
+ *             bits do not depend on the order the arrows are visited in;  v <- (1 - cov) v + cov arrow_rgb.  An arrow that leaves the image
+ *             is clipped by not being drawn there.
+ * uint8 outputs are the value rounded half up and clamped to [0, 255], fp32 outputs the value.  A pixel that no layer covers, and every pixel
+ * with layers = 0, is the input's bits.
+ * h_hw = HOST [batch][2] (H, W), each >= 1, H W < 2^31; h_img, h_up, h_lat, h_out = HOST arrays of `batch` DEVICE pointers; dtype PF_PANO_U8 |
+ * PF_PANO_F32; spacing >= 1, one per call; arrow_len_rel in [0, 1e6]; line_width finite and >= 0; lat_step_deg finite and > 0; alpha in [0, 1]; h_arrow_rgb = HOST
+ * [3] finite; layers = PF_DRAW_UP | PF_DRAW_LAT or less.  Workspace of pf_draw_fields_workspace_bytes (0 for arguments pf_draw_fields
+ * rejects): a 64-byte record per anchor, written once per call.  Argument errors return PF_ERR_ARG before any device work.  Two launches per 32
+ * images (one without PF_DRAW_UP) on `stream`, no atomics, no host-to-device copy, no host synchronisation; stateless, no handle.  Every output
+ * pixel depends on its own image and fields only: the same bits in any batch and on every run. */
+#define PF_DRAW_UP 1
+#define PF_DRAW_LAT 2
+#define PF_DRAW_RAMP {{33.f, 102.f, 172.f}, {146.f, 197.f, 222.f}, {247.f, 247.f, 247.f}, {244.f, 165.f, 130.f}, {178.f, 24.f, 43.f}}
+#define PF_DRAW_LINE_RGB {32.f, 32.f, 32.f}
+#define PF_DRAW_GRAD_FLOOR 1e-6f      /* degrees per pixel: no iso-line where the latitude is flatter */
+#define PF_DRAW_HEAD_ANGLE_DEG 25.0   /* of a barb against the shaft */
+#define PF_DRAW_HEAD_COS 0.9063078f   /* the fp32 values nearest cos and sin of it */
+#define PF_DRAW_HEAD_SIN 0.42261827f
+#define PF_DRAW_HEAD_RATIO 0.35f      /* length of a barb in shaft lengths */
+size_t pf_draw_fields_workspace_bytes(int batch, const int32_t* h_hw /*[batch][2]*/, int spacing);
+int pf_draw_fields(int device, int batch, const int32_t* h_hw /*[batch][2]*/, const void* const* h_img, const float* const* h_up,
+                   const float* const* h_lat, void* const* h_out, int dtype /*PF_PANO_U8|PF_PANO_F32*/, int spacing, float arrow_len_rel /*of W*/,
+                   float lat_step_deg, float alpha, float line_width, const float* h_arrow_rgb /*[3]*/, int layers /*PF_DRAW_UP|PF_DRAW_LAT*/,
+                   void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Predicted perspective fields against ground truth on the device: per-pixel errors, per-image statistics with an exact median, and
  * a running histogram for dataset statistics (field_err.hip).
  * Inputs per image: up_pred, up_gt [2][H][W] and lat_pred, lat_gt [H][W] degrees, fp32 (the layout of pred_gravity_original /

@@ -8,7 +8,7 @@ Sub-modules: config (zoo / cfg), schema (checkpoint keys), synth (seeded checkpo
 engine (ctypes binding of libpf_hip.so), ops (kernel-level entry points), dist (image-level data
 parallelism), build (hipcc build of csrc/).
 """
-__all__ = ["PerspectiveFields", "model_zoo", "fields_from_params", "fit_camera_params", "fit_camera_shared", "crop_panorama", "reproject_image", "compose_panorama", "yaw_scores", "align_yaw", "yaw_tree", "placement_scores", "field_errors", "FieldErrorAccumulator"]
+__all__ = ["PerspectiveFields", "model_zoo", "fields_from_params", "fit_camera_params", "fit_camera_shared", "crop_panorama", "reproject_image", "compose_panorama", "yaw_scores", "align_yaw", "yaw_tree", "placement_scores", "draw_perspective_fields", "draw_camera", "field_errors", "FieldErrorAccumulator"]
 
 
 def __getattr__(name):  # lazy: keeps `import perspectivefields_amd.synth` free of torch
@@ -48,6 +48,10 @@ def __getattr__(name):  # lazy: keeps `import perspectivefields_amd.synth` free 
         from .perspectivefields import placement_scores
 
         return placement_scores
+    if name in ("draw_perspective_fields", "draw_camera"):
+        from . import perspectivefields as _pfm
+
+        return getattr(_pfm, name)
     if name == "field_errors":
         from .perspectivefields import field_errors
 

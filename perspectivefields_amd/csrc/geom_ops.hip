@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -371,6 +371,91 @@ int pf_place_scores(int device, int n_bg, const float* const* bg_up, const float
     launch_place_sum(pb, s);
   }
   if (hipGetLastError() != hipSuccess) { g_create_error = "pf_place_scores: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+// pf_draw_fields: workspace = every image's arrow records, [ny][nx] of 64 bytes, each region 256-byte aligned
+struct DrawDims { int nx, ny; };
+// anchors (j s + s / 2, i s + s / 2) inside an H x W image
+static DrawDims draw_dims(int H, int W, int s) {
+  const long long half = s / 2;
+  return DrawDims{W > half ? (int)((W - half + s - 1) / s) : 0, H > half ? (int)((H - half + s - 1) / s) : 0};
+}
+static size_t draw_rec_bytes(int H, int W, int s) {
+  const DrawDims d = draw_dims(H, W, s);
+  return yaw_align((size_t)d.nx * d.ny * DrawBatch::REC * sizeof(float4));
+}
+// NULL, or what is wrong with the arguments that set the workspace's layout
+static const char* draw_layout_error(int B, const int32_t* hw, int spacing, std::string* why) {
+  if (B < 1 || !hw) return "batch >= 1 and h_hw are required";
+  if (spacing < 1) { *why = fmt("spacing %d, must be >= 1", spacing); return why->c_str(); }
+  for (int i = 0; i < B; ++i) {
+    const int H = hw[2 * i], W = hw[2 * i + 1];
+    if (H < 1 || W < 1 || H > (1 << 30) || W > (1 << 30) || (long long)H * W > INT32_MAX) {
+      *why = fmt("image %d is %d x %d, smaller than 1 x 1 or of 2^31 pixels or more", i, H, W);
+      return why->c_str();
+    }
+  }
+  return nullptr;
+}
+
+size_t pf_draw_fields_workspace_bytes(int B, const int32_t* hw, int spacing) {
+  std::string why;
+  if (draw_layout_error(B, hw, spacing, &why)) return 0;
+  size_t n = 256;  // alignment of the caller's pointer
+  for (int i = 0; i < B; ++i) n += draw_rec_bytes(hw[2 * i], hw[2 * i + 1], spacing);
+  return n;
+}
+
+int pf_draw_fields(int device, int B, const int32_t* hw, const void* const* img, const float* const* up, const float* const* lat, void* const* out, int dtype,
+                   int spacing, float arrow_len_rel, float lat_step_deg, float alpha, float line_width, const float* arrow_rgb, int layers, void* ws,
+                   size_t ws_bytes, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_draw_fields: " + m; return PF_ERR_ARG; };
+  std::string why;
+  if (const char* e = draw_layout_error(B, hw, spacing, &why)) return bad(e);
+  if (!img || !up || !lat || !out || !arrow_rgb) return bad("h_img, h_up, h_lat, h_out and h_arrow_rgb are required");
+  if (dtype != PF_PANO_U8 && dtype != PF_PANO_F32) return bad(fmt("unknown dtype %d", dtype));
+  if (layers < 0 || layers > (PF_DRAW_UP | PF_DRAW_LAT)) return bad(fmt("layers %d, must be a sum of PF_DRAW_UP and PF_DRAW_LAT", layers));
+  if (!(lat_step_deg > 0.f && std::isfinite(lat_step_deg))) return bad("lat_step_deg must be finite and > 0");
+  if (!(alpha >= 0.f && alpha <= 1.f)) return bad("alpha must be in [0, 1]");
+  if (!(arrow_len_rel >= 0.f && arrow_len_rel <= 1e6f)) return bad("arrow_len_rel must be in [0, 1e6]");
+  if (!(line_width >= 0.f && std::isfinite(line_width))) return bad("line_width must be finite and >= 0");
+  if (!(std::isfinite(arrow_rgb[0]) && std::isfinite(arrow_rgb[1]) && std::isfinite(arrow_rgb[2]))) return bad("h_arrow_rgb must be finite");
+  for (int i = 0; i < B; ++i)
+    if (!img[i] || !up[i] || !lat[i] || !out[i]) return bad(fmt("NULL image, field or output pointer of image %d", i));
+  const bool arrows = (layers & PF_DRAW_UP) != 0;
+  const size_t need = pf_draw_fields_workspace_bytes(B, hw, spacing);
+  if (arrows && (!ws || ws_bytes < need)) return bad(fmt("needs %zu workspace bytes, got %zu", need, ws_bytes));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uintptr_t mask = dtype == PF_PANO_U8 ? 3 : 15;
+  for (int i0 = 0; i0 < B; i0 += DrawBatch::MAX) {
+    DrawBatch db;
+    db.n = std::min(B - i0, (int)DrawBatch::MAX);
+    db.spacing = spacing; db.layers = layers; db.max_tiles = 0; db.max_anchors = 0;
+    db.lat_step = lat_step_deg; db.alpha = alpha; db.line_width = line_width;
+    for (int c = 0; c < 3; ++c) db.rgb[c] = arrow_rgb[c];
+    for (int k = 0; k < db.n; ++k) {
+      const int i = i0 + k, H = hw[2 * i], W = hw[2 * i + 1];
+      const DrawDims d = arrows ? draw_dims(H, W, spacing) : DrawDims{0, 0};
+      db.H[k] = H; db.W[k] = W; db.nx[k] = d.nx; db.ny[k] = d.ny;
+      db.len[k] = arrow_len_rel * (float)W;
+      // no pixel further than this from an anchor's pixel, along a row or a column, is covered by its arrow; beyond the image's sides every value says the same
+      db.reach[k] = (int)std::min(std::ceil((double)db.len[k] * (1.0 + (double)PF_DRAW_HEAD_RATIO) + (double)line_width + 1.0), (double)std::max(H, W));
+      db.vec[k] = (W % 4 == 0 && ((misalign(img[i], mask) | misalign(out[i], mask)) == 0)) ? 1 : 0;
+      db.fvec[k] = (W % 4 == 0 && ((misalign(up[i], 15) | misalign(lat[i], 15)) == 0)) ? 1 : 0;  // the second up plane starts H W floats on: aligned too
+      db.img[k] = img[i]; db.up[k] = up[i]; db.lat[k] = lat[i]; db.out[k] = out[i];
+      db.rec[k] = reinterpret_cast<float4*>(p);
+      if (arrows) p += draw_rec_bytes(H, W, spacing);
+      db.max_tiles = std::max(db.max_tiles, ((W - 1) / 64 + 1) * ((H - 1) / 16 + 1));
+      db.max_anchors = std::max(db.max_anchors, d.nx * d.ny);
+    }
+    launch_draw_fields(db, dtype, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_draw_fields: kernel launch failed"; return PF_ERR_DEVICE; }
   return PF_OK;
 }
 

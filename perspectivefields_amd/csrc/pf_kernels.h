@@ -567,6 +567,30 @@ void launch_place_score(const PlaceBatch& pb, hipStream_t s);  // the store pass
 void launch_place_sum(const PlaceBatch& pb, hipStream_t s);    // the chunks of each placement added in chunk order in fp64
 static_assert(sizeof(PlacePair) == 56 && sizeof(PlaceBatch) <= 4096 && sizeof(PlacePack) <= 4096, "PlaceBatch and PlacePack fit the kernel arguments");
 
+// perspective fields drawn over their images (draw_fields.hip, include/pf_hip.h pf_draw_fields): up to DrawBatch::MAX images per launch, per-image sizes
+// and pointers in the kernel arguments
+struct DrawBatch {
+  static constexpr int MAX = 32;
+  static constexpr int CAP = 128;  // arrow records per LDS batch of a tile, 64 bytes each
+  static constexpr int REC = 4;    // float4s of one record: (a, u), (tip, valid, -), (barb directions), (padded box x0, y0, x1, y1)
+  int n, spacing, layers;          // images of this launch; anchor spacing; PF_DRAW_UP | PF_DRAW_LAT
+  int max_tiles, max_anchors;      // largest number of 64 x 16 tiles and of anchors among the images: the grids
+  float lat_step, alpha, line_width, rgb[3];
+  int H[MAX], W[MAX];
+  int nx[MAX], ny[MAX];            // anchors across and down (0 without PF_DRAW_UP)
+  int reach[MAX];                  // pixels: no arrow is drawn further from its anchor's pixel than this
+  int vec[MAX];                    // 1: W % 4 == 0 and image and output aligned for the 4-pixel vector loads and stores (uint8 4 bytes, fp32 16)
+  int fvec[MAX];                   // 1: W % 4 == 0 and up and lat aligned to 16 bytes: 16-byte loads of the field planes
+  float len[MAX];                  // L = arrow_len_rel W
+  const void* img[MAX];            // (H, W, 3) uint8 or fp32
+  const float* up[MAX];            // (2, H, W)
+  const float* lat[MAX];           // (H, W) degrees
+  void* out[MAX];                  // (H, W, 3), may be img
+  float4* rec[MAX];                // [ny][nx][REC]
+};
+void launch_draw_fields(const DrawBatch& db, int dtype, hipStream_t s);  // the arrow records (with PF_DRAW_UP), then the tiles
+static_assert(sizeof(DrawBatch) <= 4096, "DrawBatch fits the kernel arguments");
+
 // predicted fields against ground truth (field_err.hip, include/pf_hip.h pf_field_errors): up to FerrBatch::MAX images per launch,
 // per-image sizes and pointers in the kernel arguments
 constexpr int FERR_REC = 10;         // doubles of one accumulate block's partial record

@@ -75,6 +75,8 @@ _SIGNATURES = {
     "pf_yaw_moments": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
     "pf_place_scores_workspace_bytes": (_c.c_size_t, [_c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int]),
     "pf_place_scores": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _P, _P, _P, _c.c_int, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
+    "pf_draw_fields_workspace_bytes": (_c.c_size_t, [_c.c_int, _P, _c.c_int]),
+    "pf_draw_fields": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_float, _P, _c.c_int, _P, _c.c_size_t, _P]),
     "pf_field_errors_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
     "pf_field_errors": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_float, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
     "pf_profile_begin": (_c.c_int, [_P, _c.c_uint]),
