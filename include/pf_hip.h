@@ -485,6 +485,41 @@ int pf_pano_compose(int device, int n_view, const void* const* h_view, const int
                     void* d_pano /*[n_pano][Hp][Wp][3]*/, float* d_weight /*[n_pano][Hp][Wp] or NULL*/,
                     float* d_acc /*[n_pano][Hp][Wp][4] fp32 workspace; may be NULL unless a panorama has more than 32 views*/, void* stream);
 
+/* Equirectangular panoramas rotated into equirectangular panoramas on the device, with the perspective fields of the panoramic camera:
+ * levelling a tilted panorama, tilting an upright one (labelled data), re-centring a composite (pano_rotate.hip).
+ * Conventions of pf_pano_crop and pf_pano_compose: x right, y down, z forward, world up = (0, -1, 0), R(r, p) = R_pitch(p) R_roll(r) camera ->
+ * world, Y(psi) = [[cos psi, 0, sin psi], [0, 1, 0], [-sin psi, 0, cos psi]] the turn about y that adds psi to the longitude.
+ * Per output theta = d_rot3 row = {roll r, pitch p, yaw psi} (RADIANS), DEVICE [batch][3], and one flag `inverse` per call:
+ *   Q = Y(psi) R(r, p), A = Q, or Q^T with inverse != 0.
+ * For pixel (row, col) of an H x W output (pf_pano_compose's direction of a panorama pixel):
+ *   lon = ((col + 1/2)/W - 1/2) 2 pi, lat = (1/2 - (row + 1/2)/H) pi, D = (cos lat sin lon, -sin lat, cos lat cos lon)
+ *   1 source    X = A D; lat_s = -atan2(X.y, hypot(X.x, X.z)), lon_s = atan2(X.x, X.z); u = (lon_s/2pi + 1/2) Ws - 1/2, v = (1/2 - lat_s/pi) Hs - 1/2
+ *               of the source Hs x Ws (each >= 2), pixel centres at integers
+ *   2 image     bilinear at (u, v), columns wrap modulo Ws, rows clamp to [0, Hs - 1] (pf_pano_crop's sampling); PF_PANO_U8: the fp32 value
+ *               rounded half up, clamped to [0, 255]; PF_PANO_F32: the value
+ *               inverse = 0: what a panoramic camera with orientation (r, p, psi) inside an upright source sees;
+ *               inverse != 0: a source shot by such a camera becomes the upright panorama (levelling)
+ *   3 labels    the perspective fields of a panoramic camera whose camera -> world rotation is A (layout of pred_gravity_original /
+ *               pred_latitude_original): latitude = lat_s in degrees, at the pixel centre; up = the image direction of a step along world up:
+ *               g = A^T (0, -1, 0), t = g - (g . D) D, e_lon = (cos lon, 0, -sin lon), e_lat = (-sin lat sin lon, -cos lat, -sin lat cos lon),
+ *               up ~ (W/(2 pi) (t . e_lon) / cos lat, -H/pi (t . e_lat)) normalised; |t|^2 = (t . e_lon)^2 + (t . e_lat)^2 < PF_PANO_UP_MIN_T2 (a
+ *               pixel centre on the zenith or nadir of the world): up = NaN, the latitude stays
+ * Non-finite r, p or psi: the output's image is 0 and its labels NaN, and no load is issued for it (pf_pano_crop's rule for a pixel without
+ * a ray); every other output keeps its bits.  No antialiasing: a strong minification aliases.
+ * pf_pano_rotate: h_pano = HOST array of n_pano DEVICE pointers, (Hs, Ws, 3) channel-interleaved, all of type `dtype`; h_pano_hw = HOST
+ * [n_pano][2] (Hs, Ws); h_pano_index = HOST [batch], the source of each output.  d_img = DEVICE [batch][H][W][3] of `dtype` (required); d_up
+ * [batch][2][H][W] and d_lat [batch][H][W] fp32: both or neither (NULL: no labels).  pf_pano_fields: the labels alone, no source; its bits
+ * are those of pf_pano_rotate's labels for the same d_rot3 row, inverse, H and W.
+ * Argument errors (NULL required pointers, n_pano < 1, batch < 1, a source side < 2, H or W < 1, a bad dtype, an index out of range, one of
+ * d_up / d_lat alone) return PF_ERR_ARG before any device work.  One launch per 32 outputs on `stream`, no host synchronisation; stateless, no
+ * handle; deterministic, each output's bits independent of the batch it is in. */
+#define PF_PANO_UP_MIN_T2 1e-10f
+int pf_pano_rotate(int device, int n_pano, const void* const* h_pano, const int32_t* h_pano_hw /*[n_pano][2]*/, int dtype, int batch,
+                   const int32_t* h_pano_index /*[batch]*/, const float* d_rot3 /*[batch][3] roll, pitch, yaw, radians*/, int inverse, int H, int W,
+                   void* d_img /*[batch][H][W][3], dtype*/, float* d_up /*[batch][2][H][W]*/, float* d_lat /*[batch][H][W]*/, void* stream);
+int pf_pano_fields(int device, int batch, const float* d_rot3 /*[batch][3]*/, int inverse, int H, int W, float* d_up /*[batch][2][H][W]*/,
+                   float* d_lat /*[batch][H][W]*/, void* stream);
+
 /* The relative yaw of camera views of one centre, from the pictures: for ordered pairs (a, b) of views and a list of candidate turns, the moments of
  * the two luminance images on their overlap, from which the zero-mean normalised cross-correlation follows (yaw_align.hip).
  * The fields give roll, pitch and intrinsics of a view but not the direction it faces; with those known, two views of one centre differ by a single

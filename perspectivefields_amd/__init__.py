@@ -3,12 +3,13 @@
     from perspectivefields_amd import PerspectiveFields      # or: from perspective2d import PerspectiveFields
     m = PerspectiveFields("Paramnet-360Cities-edina-centered").eval().cuda()
     pred = m.inference(img_bgr)
+    upright = m.level_panorama(pano)                          # rotate_panorama / panorama_fields / gravity_from_views: panorama -> panorama
 
 Sub-modules: config (zoo / cfg), schema (checkpoint keys), synth (seeded checkpoints and images),
 engine (ctypes binding of libpf_hip.so), ops (kernel-level entry points), dist (image-level data
 parallelism), build (hipcc build of csrc/).
 """
-__all__ = ["PerspectiveFields", "model_zoo", "fields_from_params", "fit_camera_params", "fit_camera_shared", "crop_panorama", "reproject_image", "compose_panorama", "yaw_scores", "align_yaw", "yaw_tree", "placement_scores", "draw_perspective_fields", "draw_camera", "field_errors", "FieldErrorAccumulator"]
+__all__ = ["PerspectiveFields", "model_zoo", "fields_from_params", "fit_camera_params", "fit_camera_shared", "crop_panorama", "reproject_image", "compose_panorama", "rotate_panorama", "panorama_fields", "gravity_from_views", "yaw_scores", "align_yaw", "yaw_tree", "placement_scores", "draw_perspective_fields", "draw_camera", "field_errors", "FieldErrorAccumulator"]
 
 
 def __getattr__(name):  # lazy: keeps `import perspectivefields_amd.synth` free of torch
@@ -40,6 +41,10 @@ def __getattr__(name):  # lazy: keeps `import perspectivefields_amd.synth` free 
         from .perspectivefields import compose_panorama
 
         return compose_panorama
+    if name in ("rotate_panorama", "panorama_fields", "gravity_from_views"):
+        from . import perspectivefields as _pfm
+
+        return getattr(_pfm, name)
     if name in ("yaw_scores", "align_yaw", "yaw_tree"):
         from . import perspectivefields as _pfm
 

@@ -1,4 +1,4 @@
-// What the batched image gathers (pano_crop.hip, reproject.hip, pano_compose.hip) share on the device: the bilinear blend of four taps, the uint8 rounding rule and
+// What the batched image gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip) share on the device: the bilinear blend of four taps, the uint8 rounding rule and
 // the stores of the RGB epilogue.  Each kernel keeps its camera model and its index policy (which taps); the blend's order of operations and the
 // rounding are here alone, so that every gather gives the same bits for the same taps.  The launch's shape is GatherDims (pf_kernels.h).
 // yaw_align.hip samples one-channel fp32 planes with the same tap rule and blend order (sample_clamped_plane).
@@ -38,6 +38,21 @@ __device__ __forceinline__ void sample_clamped(const T* __restrict__ src, int Hs
   const int c0 = min(max(c, 0), Ws - 1), c1 = min(max(c + 1, 0), Ws - 1);
   const int r0 = min(max(r, 0), Hs - 1), r1 = min(max(r + 1, 0), Hs - 1);
   bilerp_rgb(src, Ws, r0, r1, c0, c1, fu, fv, out);
+}
+
+// bilinear sample of channel-interleaved (Hp, Wp, 3) texels at (u, v): columns wrap, rows clamp, every index is forced into the panorama
+template <typename T>
+__device__ __forceinline__ void sample(const T* __restrict__ pano, int Hp, int Wp, float u, float v, float* out) {
+  const float uf = floorf(u), vf = floorf(v);
+  const float fu = u - uf, fv = v - vf;
+  int c0 = (int)uf;
+  c0 = c0 < 0 ? c0 + Wp : c0;
+  c0 = c0 >= Wp ? c0 - Wp : c0;
+  c0 = (unsigned)c0 >= (unsigned)Wp ? 0 : c0;
+  const int c1 = c0 + 1 == Wp ? 0 : c0 + 1;
+  const int r = (int)vf;
+  const int r0 = min(max(r, 0), Hp - 1), r1 = min(max(r + 1, 0), Hp - 1);
+  bilerp_rgb(pano, Wp, r0, r1, c0, c1, fu, fv, out);
 }
 
 // the one-channel form: bilinear sample of an (Hs, Ws) fp32 plane at (u, v) with the tap rule and the blend order of sample_clamped

@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -17,7 +17,7 @@ int pf_fields_from_params(int device, const float* d_cam5, int H, int W, float* 
   return PF_OK;
 }
 
-// The host path of both image gathers (gather.h): argument checks in one order, the launch's GatherDims, launch groups of Batch::MAX outputs.
+// The host path of the one-source image gathers (gather.h): argument checks in one order, the launch's GatherDims, launch groups of Batch::MAX outputs.
 // A gather names its sources and outputs in the messages and says what it requires beyond the sources, the index and the image
 struct GatherKind {
   const char *name, *src, *out;     // "pf_pano_crop", "panorama", "crop"
@@ -98,6 +98,48 @@ int pf_reproject(int device, int n_src, const void* const* src, const int32_t* s
                       rb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
                       rb.map = d_map ? d_map + (size_t)i0 * 2 * npx : nullptr;
                     });
+}
+
+int pf_pano_rotate(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
+                   const float* d_rot3, int inverse, int H, int W, void* d_img, float* d_up, float* d_lat, void* stream) {
+  static const GatherKind kind{"pf_pano_rotate", "panorama", "output", 2, "needs at least one panorama (h_pano, h_pano_hw)",
+                               "batch >= 1, h_pano_index, d_rot3 and d_img are required"};
+  const size_t npx = (size_t)H * W;
+  return gather_run(kind, launch_pano_rotate, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_rot3 != nullptr, H, W, d_img,
+                    !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr, misalign(d_up, 15) | misalign(d_lat, 15), stream,
+                    [=](PanoRotBatch& rb, int i0) {
+                      rb.inverse = inverse ? 1 : 0;
+                      rb.rot = d_rot3 + (size_t)i0 * 3;
+                      rb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
+                      rb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
+                    });
+}
+
+// the labels of pf_pano_rotate without a source: its checks that concern the outputs, its tile and its launch groups
+int pf_pano_fields(int device, int B, const float* d_rot3, int inverse, int H, int W, float* d_up, float* d_lat, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_pano_fields: " + m; return PF_ERR_ARG; };
+  if (B < 1 || !d_rot3 || !d_up || !d_lat) return bad("batch >= 1, d_rot3, d_up and d_lat are required");
+  if (H < 1 || W < 1) return bad(fmt("output size %d x %d", H, W));
+  const int tpr = 16;  // a 64 x 16 pixel tile, as the gathers
+  const long tiles_x = (W + 4 * tpr - 1) / (4 * tpr), tiles_y = (H + 256 / tpr - 1) / (256 / tpr);
+  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("output size %d x %d too large", H, W));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  const size_t npx = (size_t)H * W;
+  const int vec = (W % 4 == 0 && (misalign(d_up, 15) | misalign(d_lat, 15)) == 0) ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i0 = 0; i0 < B; i0 += PanoFieldsBatch::MAX) {
+    PanoFieldsBatch fb;
+    fb.d = GatherDims{std::min(B - i0, (int)PanoFieldsBatch::MAX), H, W, tpr, (int)tiles_x, (int)tiles_y, vec};
+    fb.inverse = inverse ? 1 : 0;
+    fb.rot = d_rot3 + (size_t)i0 * 3;
+    fb.up = d_up + (size_t)i0 * 2 * npx;
+    fb.lat = d_lat + (size_t)i0 * npx;
+    launch_pano_fields(fb, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_pano_fields: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
 }
 
 // Several views per output, so not gather_run: the launches follow the panoramas, not the sources.  Panoramas share a launch while it holds at most

@@ -37,21 +37,6 @@ struct CropConsts {
   PinholeFields pin;  // the xi == 0 labels
 };
 
-// bilinear sample of channel-interleaved (Hp, Wp, 3) texels at (u, v): columns wrap, rows clamp, every index is forced into the panorama
-template <typename T>
-__device__ __forceinline__ void sample(const T* __restrict__ pano, int Hp, int Wp, float u, float v, float* out) {
-  const float uf = floorf(u), vf = floorf(v);
-  const float fu = u - uf, fv = v - vf;
-  int c0 = (int)uf;
-  c0 = c0 < 0 ? c0 + Wp : c0;
-  c0 = c0 >= Wp ? c0 - Wp : c0;
-  c0 = (unsigned)c0 >= (unsigned)Wp ? 0 : c0;
-  const int c1 = c0 + 1 == Wp ? 0 : c0 + 1;
-  const int r = (int)vf;
-  const int r0 = min(max(r, 0), Hp - 1), r1 = min(max(r + 1, 0), Hp - 1);
-  bilerp_rgb(pano, Wp, r0, r1, c0, c1, fu, fv, out);
-}
-
 }  // namespace
 
 template <typename T, bool LABELS>

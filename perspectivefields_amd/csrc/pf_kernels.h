@@ -484,6 +484,30 @@ void launch_reproject(const ReprojBatch& rb, int dtype, hipStream_t s);
 static_assert(sizeof(PanoBatch) == 576 && offsetof(PanoBatch, src) == 32, "PanoBatch layout");
 static_assert(sizeof(ReprojBatch) == 584 && offsetof(ReprojBatch, fill) == 28 && offsetof(ReprojBatch, src) == 32, "ReprojBatch layout");
 
+// equirectangular panorama -> rotated equirectangular panorama + the fields of the panoramic camera (pano_rotate.hip, include/pf_hip.h pf_pano_rotate)
+struct PanoRotBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int inverse;        // 0: A = Q = Y(yaw) R(roll, pitch); otherwise A = Q^T
+  GatherSources src;  // the source panoramas (Hs, Ws, 3)
+  const float* rot;   // [n][3]: roll, pitch, yaw (radians)
+  void* img;          // [n][H][W][3], the sources' type
+  float* up;          // NULL (no labels) or [n][2][H][W]
+  float* lat;         // NULL or [n][H][W] degrees
+};
+void launch_pano_rotate(const PanoRotBatch& rb, int dtype, hipStream_t s);
+static_assert(sizeof(PanoRotBatch) == 576 && offsetof(PanoRotBatch, inverse) == 28 && offsetof(PanoRotBatch, src) == 32, "PanoRotBatch layout");
+// the labels alone (pf_pano_fields): no source
+struct PanoFieldsBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int inverse;
+  const float* rot;  // [n][3]
+  float* up;         // [n][2][H][W]
+  float* lat;        // [n][H][W] degrees
+};
+void launch_pano_fields(const PanoFieldsBatch& fb, hipStream_t s);
+
 // camera views of one centre -> equirectangular panoramas (pano_compose.hip, include/pf_hip.h pf_pano_compose): the outputs of a launch are up to MAX
 // panoramas, its sources up to MAX views; panorama k blends the views [first[k], first[k] + count[k]) of the launch in that order
 struct ComposeBatch {

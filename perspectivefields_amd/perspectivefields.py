@@ -16,6 +16,7 @@ device raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import operator
 import os
 from collections import OrderedDict
@@ -579,6 +580,53 @@ class PerspectiveFields(nn.Module):
         if "mode" in kw:
             raise ValueError("align_yaw takes the angles of its preds, which are degrees: no mode")
         return align_yaw(images, PerspectiveFields._pred_cameras("align_yaw", preds), mode="deg", **kw)
+
+    def level_panorama(self, pano, *, n_yaw=8, view_pitch=(0.0,), vfov=90.0, view_size=None, use="paramnet", return_info=False, preds=None):
+        """A tilted equirectangular panorama made upright, on the GPU: n_yaw x len(view_pitch) square pinhole views of `vfov` degrees are cut out of it
+        (crop_panorama: yaw k 360 / n_yaw, the pitches of view_pitch in degrees, roll 0, view_size pixels, default the network's input size), the model
+        predicts every view's roll and pitch, `gravity_from_views` turns them into the panorama's roll and pitch, and
+        `rotate_panorama(pano, roll, pitch, inverse=True)` re-samples it.
+        pano: one CUDA tensor (H, W, 3), uint8 or float32 (on the 0 .. 255 scale; the views go to the network as uint8).
+        use: "paramnet" -- the ParamNet scalars pred_roll / pred_pitch of every view; "fit" -- `fit_camera` on every view's dense fields (the only
+        choice for a PersNet model).
+        preds: the per-view results, one dict per view in the order pitch-major, yaw-minor -- inference results, or dicts with pred_roll / pred_pitch
+        ("paramnet") or pred_gravity_original / pred_latitude_original ("fit"); given, nothing is cropped and the network does not run.
+        Returns the upright panorama (H, W, 3) in the source's dtype; with return_info=True also a dict: roll, pitch (the estimate, degrees), views
+        (the views' roll, pitch, yaw), preds (one per view, after the fit with use="fit") and gravity (gravity_from_views' result)."""
+        if use not in ("paramnet", "fit"):
+            raise ValueError("use must be 'paramnet' or 'fit'")
+        n_yaw = operator.index(n_yaw)
+        pitches = [float(v) for v in (view_pitch if isinstance(view_pitch, (list, tuple)) else [view_pitch])]
+        if n_yaw < 1 or not pitches:
+            raise ValueError("level_panorama needs n_yaw >= 1 and at least one view pitch")
+        if not (0.0 < float(vfov) < 180.0):
+            raise ValueError("vfov must be in (0, 180) degrees")
+        size = NET_H if view_size is None else int(view_size)
+        if size < 8:
+            raise ValueError("view_size must be at least 8")
+        if not torch.is_tensor(pano):
+            raise TypeError("level_panorama takes one panorama, a torch tensor (H, W, 3)")
+        _cuda_image_list("level_panorama", [pano], ("panorama", "panoramas"), "a panorama must be (H, W, 3) with H, W >= 2", 2)
+        views = {"roll": [0.0] * (n_yaw * len(pitches)), "pitch": [p for p in pitches for _ in range(n_yaw)],
+                 "yaw": [k * 360.0 / n_yaw for _ in pitches for k in range(n_yaw)]}
+        n = n_yaw * len(pitches)
+        if preds is None:
+            crops = crop_panorama(pano, 0.0, views["pitch"], 0.5 / math.tan(math.radians(float(vfov)) / 2), yaw=views["yaw"], height=size, width=size, fields=False)[0]
+            if crops.dtype != torch.uint8:
+                crops = crops.round().clamp(0, 255).to(torch.uint8)
+            preds = self.inference_batch(list(crops))
+        else:
+            preds = [preds] if isinstance(preds, dict) else list(preds)
+            if len(preds) != n:
+                raise ValueError(f"level_panorama: {len(preds)} preds for {n} views")
+        if use == "fit":
+            preds = self.fit_camera(preds)
+        cams = PerspectiveFields._pred_cameras("level_panorama", preds)
+        est = gravity_from_views(views, cams["roll"], cams["pitch"], mode="deg")
+        out = rotate_panorama(pano, est["roll"], est["pitch"], inverse=True, mode="deg")[0]
+        if not return_info:
+            return out
+        return out, {"roll": est["roll"], "pitch": est["pitch"], "views": views, "preds": preds, "gravity": est}
 
     def forward(self, batched_inputs) -> List[dict]:
         """batched_inputs: list of {"image": (3,320,320) float BGR 0..255, "height", "width"} (reference :223-272)."""
@@ -1357,6 +1405,183 @@ def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0
         _check(lib.pf_pano_crop(dev.index, len(panos), p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, cam.data_ptr(), H, W, img.data_ptr(),
                                 up.data_ptr() if fields else None, lat.data_ptr() if fields else None, _stream_ptr()), None, "pf_pano_crop")
     return img, up, lat
+
+
+def _rotation_params(fn, named):
+    """(name, value) pairs -> tensors (numbers or 1-d), checked where they are; nothing moves to the device"""
+    ts = []
+    for name, v in named:
+        t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float64))
+        if t.dim() > 1:
+            raise ValueError(f"{fn}: {name} must be a number or a 1-d sequence; got shape {tuple(t.shape)}")
+        ts.append(t)
+    return ts
+
+
+def rotate_panorama(pano, roll=0.0, pitch=0.0, yaw=0.0, *, inverse=False, height=None, width=None, pano_index=None, mode="deg", fields=False):
+    """Equirectangular panoramas -> rotated equirectangular panoramas on the GPU, with the perspective fields of the panoramic camera on request:
+    levelling a tilted 360 degree picture, tilting an upright one (labelled data for tilted panoramas), re-centring a composite.  Model, sampling and
+    labels: include/pf_hip.h pf_pano_rotate; the conventions are `crop_panorama`'s.
+
+    pano: a CUDA tensor (Hs, Ws, 3), uint8 or float32, or a list of them (one dtype, one device).
+    roll, pitch, yaw (degrees unless mode="rad"): numbers, 0-d tensors or 1-d tensors / sequences, broadcast to the batch size B (1 when all are
+    scalars); device tensors stay on the device.  With Q = Y(yaw) R_pitch(pitch) R_roll(roll):
+    inverse=False -- the output is what a panoramic camera with orientation (roll, pitch, yaw) inside the (upright) source sees;
+    inverse=True  -- a source shot by such a camera becomes the upright panorama: the levelling direction, which undoes the other.
+    pano_index: None (every output from panorama 0) or B integers.  height, width: the size of every output, default the sources' (required
+    when they differ in size).
+    Returns the images (B, H, W, 3) in the panorama's dtype; with fields=True (images, up (B, 2, H, W), lat (B, H, W) degrees), the perspective
+    fields of the output's camera in the layout of pred_gravity_original / pred_latitude_original (up is NaN at a pixel centre on the world's zenith
+    or nadir).  Non-finite angles give an image of 0 and NaN fields.  GPU only: CPU panoramas raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    panos, dev = _cuda_image_list("rotate_panorama", [pano] if torch.is_tensor(pano) else list(pano), ("panorama", "panoramas"),
+                                  "a panorama must be (Hs, Ws, 3) with Hs, Ws >= 2", 2)
+    sizes = [(int(p.shape[0]), int(p.shape[1])) for p in panos]
+    if (height is None) != (width is None):
+        raise ValueError("rotate_panorama: height and width are both given or both left out")
+    if height is None:
+        if len(set(sizes)) != 1:
+            raise ValueError("rotate_panorama: the panoramas differ in size, so height and width are required")
+        H, W = sizes[0]
+    else:
+        H, W = int(height), int(width)
+    if H < 1 or W < 1:
+        raise ValueError(f"output size must be at least 1 x 1; got {H} x {W}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    ts = _rotation_params("rotate_panorama", (("roll", roll), ("pitch", pitch), ("yaw", yaw)))
+    B = _broadcast_len("rotate_panorama", ts)
+    if B < 1:
+        raise ValueError("rotate_panorama needs at least one output")
+    if pano_index is None:
+        idx = [0] * B
+    else:
+        idx = [operator.index(i) for i in (pano_index.tolist() if torch.is_tensor(pano_index) else pano_index)]
+        if len(idx) != B:
+            raise ValueError(f"pano_index has {len(idx)} entries for {B} outputs")
+        if any(i < 0 or i >= len(panos) for i in idx):
+            raise ValueError(f"pano_index entries must be in [0, {len(panos)})")
+    rot = _camera_rows(ts, (0, 1, 2), B, dev, mode).contiguous()
+    panos = [p.contiguous() for p in panos]
+    img = torch.empty((B, H, W, 3), dtype=panos[0].dtype, device=dev)
+    up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if fields else None
+    lat = torch.empty((B, H, W), dtype=torch.float32, device=dev) if fields else None
+    p_pano, hw, c_idx = _source_arrays(panos, sizes, idx)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_pano_rotate(dev.index, len(panos), p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, rot.data_ptr(), 1 if inverse else 0, H, W,
+                                  img.data_ptr(), up.data_ptr() if fields else None, lat.data_ptr() if fields else None, _stream_ptr()), None, "pf_pano_rotate")
+    return (img, up, lat) if fields else img
+
+
+def panorama_fields(roll, pitch, *, height, width, mode="deg", device=None):
+    """The perspective fields of an equirectangular (panoramic) camera with the given roll and pitch on the GPU: the counterpart of
+    `fields_from_params` for the equirectangular projection, and the labels of `rotate_panorama(..., fields=True)` for the same parameters, bit for
+    bit (yaw does not enter).  Model: include/pf_hip.h pf_pano_fields.
+    roll, pitch (degrees unless mode="rad"): numbers, 0-d tensors or 1-d tensors / sequences, broadcast to B.  Returns (up (B, 2, H, W) unit vectors,
+    latitude (B, H, W) degrees); up is NaN at a pixel centre on the zenith or nadir.  device: a CUDA device, default that of a tensor argument,
+    else the current one."""
+    from .engine import _check, _stream_ptr, load_library
+
+    H, W = int(height), int(width)
+    if H < 1 or W < 1:
+        raise ValueError(f"field size must be at least 1 x 1; got {H} x {W}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    ts = _rotation_params("panorama_fields", (("roll", roll), ("pitch", pitch), ("yaw", 0.0)))
+    B = _broadcast_len("panorama_fields", ts)
+    if B < 1:
+        raise ValueError("panorama_fields needs at least one camera")
+    if device is None:
+        device = next((t.device for t in ts if t.is_cuda), None)
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise PfError("panorama_fields runs on the GPU only (no CPU path)")
+    if not torch.cuda.is_available():
+        raise PfError("panorama_fields runs on the GPU only and no GPU is available")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    rot = _camera_rows(ts, (0, 1, 2), B, dev, mode).contiguous()
+    up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+    lat = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_pano_fields(dev.index, B, rot.data_ptr(), 0, H, W, up.data_ptr(), lat.data_ptr(), _stream_ptr()), None, "pf_pano_fields")
+    return up, lat
+
+
+def _rot_roll_pitch(roll, pitch):
+    """R = R_pitch(pitch) R_roll(roll), camera -> world, for fp64 tensors (..., ) of radians -> (..., 3, 3)"""
+    cr, sr, cp, sp = torch.cos(roll), torch.sin(roll), torch.cos(pitch), torch.sin(pitch)
+    z = torch.zeros_like(cr)
+    return torch.stack([torch.stack([cr, -sr, z], -1), torch.stack([cp * sr, cp * cr, -sp], -1), torch.stack([sp * sr, sp * cr, cp], -1)], -2)
+
+
+def _rot_yaw(yaw):
+    """Y(yaw), the turn about y that adds yaw to the longitude"""
+    c, s = torch.cos(yaw), torch.sin(yaw)
+    z, o = torch.zeros_like(c), torch.ones_like(c)
+    return torch.stack([torch.stack([c, z, s], -1), torch.stack([z, o, z], -1), torch.stack([-s, z, c], -1)], -2)
+
+
+def gravity_from_views(view_cams, roll, pitch, *, weights=None, max_dev=15.0, mode="deg"):
+    """The roll and pitch of a panorama from what was said about views cut out of it: every view's up direction, carried into the panorama's frame
+    and averaged robustly.  Pure torch in fp64 on the device of its inputs (CPU or GPU); no host synchronisation.
+
+    view_cams: a dict of the per-view `roll`, `pitch`, `yaw` with which the views were cut from one panorama (`crop_panorama`'s arguments; absent
+    entries count as 0).  roll, pitch: what the model (pred_roll, pred_pitch) or `fit_camera` said about each view, N values.  Angles in degrees
+    unless mode="rad"; max_dev and the returned `angles` are always degrees.
+    View i votes v_i = V_i R(roll_i, pitch_i)^T (0, -1, 0) with V_i = Y(yaw_i) R(view roll_i, view pitch_i): the world's up in the panorama's
+    frame.  The result is the weighted mean direction (weights: N values >= 0, default 1), re-averaged once over the views within max_dev
+    degrees of it, and returned as the (roll, pitch) with R(roll, pitch)^T (0, -1, 0) = that direction -- what
+    `rotate_panorama(pano, roll, pitch, inverse=True)` levels the panorama with.  A view with a non-finite prediction, camera or weight does not vote;
+    without a voting view the result is NaN.
+    Returns a dict: roll, pitch (0-d, in `mode` units), direction (3,), votes (N, 3; NaN rows for views that do not vote), inliers (N,) bool,
+    angles (N,) degrees between each vote and the result."""
+    if not isinstance(view_cams, Mapping):
+        raise TypeError(f"gravity_from_views: view_cams must be a dict of roll, pitch, yaw; got {type(view_cams).__name__}")
+    unknown = [k for k in view_cams if k not in ("roll", "pitch", "yaw")]
+    if unknown:
+        raise ValueError(f"gravity_from_views: view_cams may hold roll, pitch and yaw; unknown {unknown}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    if not (float(max_dev) > 0.0):
+        raise ValueError("max_dev must be > 0 degrees")
+    named = [("view roll", view_cams.get("roll", 0.0)), ("view pitch", view_cams.get("pitch", 0.0)), ("view yaw", view_cams.get("yaw", 0.0)),
+             ("roll", roll), ("pitch", pitch), ("weights", 1.0 if weights is None else weights)]
+    ts = _rotation_params("gravity_from_views", named)
+    N = _broadcast_len("gravity_from_views", ts)
+    if N < 1:
+        raise ValueError("gravity_from_views needs at least one view")
+    dev = next((t.device for t in ts if t.device.type != "cpu"), torch.device("cpu"))
+    ts = [t.to(device=dev, dtype=torch.float64).expand(N) for t in ts]
+    vr, vp, vy, r, p = [torch.deg2rad(t) if mode == "deg" else t for t in ts[:5]]
+    w = ts[5]
+    up = torch.tensor([0.0, -1.0, 0.0], dtype=torch.float64, device=dev)
+    votes = (_rot_yaw(vy) @ _rot_roll_pitch(vr, vp) @ _rot_roll_pitch(r, p).transpose(-1, -2)) @ up
+    voting = torch.isfinite(votes).all(-1) & torch.isfinite(w) & (w >= 0)
+    v0 = torch.where(voting[:, None], votes, torch.zeros_like(votes))
+    w0 = torch.where(voting, w, torch.zeros_like(w))
+
+    def mean_dir(wk):
+        s = (wk[:, None] * v0).sum(0)
+        return s / torch.linalg.vector_norm(s)   # 0 / 0 = NaN without a voting view
+
+    def angles_to(d):
+        return torch.rad2deg(torch.atan2(torch.linalg.vector_norm(torch.linalg.cross(votes, d.expand_as(votes)), dim=-1), votes @ d))
+
+    first = mean_dir(w0)
+    near = voting & (angles_to(first) <= float(max_dev))
+    d = mean_dir(torch.where(near, w0, torch.zeros_like(w0)))
+    d = torch.where(torch.isfinite(d).all(), d, first)   # no view within max_dev of the first mean: it stands
+    ang = angles_to(d)
+    # R(roll, pitch)^T (0, -1, 0) = (-cos p sin r, -cos p cos r, sin p)
+    out_pitch = torch.atan2(d[2], torch.linalg.vector_norm(d[:2]))
+    out_roll = torch.atan2(-d[0], -d[1])
+    if mode == "deg":
+        out_roll, out_pitch = torch.rad2deg(out_roll), torch.rad2deg(out_pitch)
+    return {"roll": out_roll, "pitch": out_pitch, "direction": d, "votes": votes, "inliers": voting & (ang <= float(max_dev)), "angles": ang}
 
 
 _CAM_KEYS = ("roll", "pitch", "yaw", "rel_focal", "rel_cx", "rel_cy", "xi")   # the row order of pf_reproject's d_cam_src7 / d_cam_dst7
