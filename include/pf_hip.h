@@ -780,6 +780,38 @@ int pf_op_sr_attention_variant(int device, int variant, const float* d_q, const 
 int pf_op_upsample2x(int device, const float* d_x, float* d_y, int B, int H, int W, int C, uint16_t* d_y_planes, long plane_elems, void* stream);
 int pf_op_num_conv_tiles(void);
 const char* pf_op_conv_tile_name(int tile_id);
+/* ---- the kernels at the two ends of the forward, one entry each (tests/test_gpu_head_tail.py).  d_* are the caller's DEVICE buffers, h_* HOST arrays in the
+ * reference's shapes.  Every argument a kernel cannot take (NULL, a size below 1, a pointer of a 16-byte access that is not 16-byte aligned, the limits named
+ * below) returns PF_ERR_ARG before any device work.  One launch on `stream`; the entries without host weights do not synchronise, those with host weights wait
+ * for the stream before they free their uploaded copies, as every pf_op_* entry with host weights does. */
+/* input normalisation (perspectivefields.py:234-236): y (B, H, W, 4) = ((x - mean) / std, channel 3 = 0); x uint8 (B, H, W, 3), or fp32 planar (B, 3, H, W) */
+int pf_op_prep_u8(int device, const uint8_t* d_x, int B, int H, int W, const float* h_mean3, const float* h_std3 /*non-zero*/, float* d_y, void* stream);
+int pf_op_prep_f32_nchw(int device, const float* d_x, int B, int H, int W, const float* h_mean3, const float* h_std3 /*non-zero*/, float* d_y, void* stream);
+/* the stand-alone regression prediction heads (gravity_head.py:117,190-193; latitude_head.py:118,189-192): 32-channel features tg, tl (B, HW, 32) ->
+ * pg (B, 2, HW) = F.normalize(tg wg^T + bg) (eps 1e-12), pl (B, HW) = clamp(tl wl^T + bl, -1, 1), and, when d_pn != NULL, pn (B HW, 4) = (g0, g1, lat, 0) */
+int pf_op_pred_regression(int device, const float* d_tg, const float* d_tl, int B, int HW, const float* h_wg /*[2][32]*/, const float* h_bg /*[2]*/,
+                          const float* h_wl /*[1][32]*/, const float* h_bl /*[1]*/, float* d_pg, float* d_pl, float* d_pn /*or NULL*/, void* stream);
+/* argmax decode of the classification heads (utils/utils.py:114-130,148-162): logits (B, ng, HW) / (B, nl, HW) -> dg (B, 2, HW) = (cos, sin) of bin * 360 / (ng - 1) - 180
+ * degrees, (0, 0) for the last ("invalid") bin; dl (B, HW) = -90 + (bin + 1/2) 180 / nl degrees.  The first maximum wins, as torch.argmax; ng >= 2, nl >= 1; NaN logits
+ * are outside the contract. */
+int pf_op_decode_cls(int device, const float* d_logit_g, int ng, const float* d_logit_l, int nl, int B, int HW, float* d_dg, float* d_dl, void* stream);
+/* F.interpolate(x, (Ho, Wo)) in its default (legacy) 'nearest' mode on NHWC4 data (param_network.py:197): x (B, H, W, 4) -> y (B, Ho, Wo, 4), different buffers */
+int pf_op_nearest_nhwc4(int device, const float* d_x, int B, int H, int W, int Ho, int Wo, float* d_y, void* stream);
+/* the ConvNeXt tail (convnext.py:144-151): y (B, nout) = Linear(LayerNorm(mean over HW of x (B, HW, C))).  1 <= C <= 1024: the pooled row lives in a fixed LDS array. */
+int pf_op_gap_ln_head(int device, const float* d_x, int B, int HW, int C, const float* h_gamma, const float* h_beta, float eps, const float* h_head_w /*[nout][C]*/,
+                      const float* h_head_b, int nout, float* d_y, void* stream);
+/* raw ParamNet outputs (B, nraw) -> (B, PF_PARAMS_STRIDE) (param_network.py:62-67 / 204-220).  mode 0 (needs nraw >= 4): raw 0..2 x 90, 1 / (2 tan raw2), raw 0..3;
+ * mode 1: the raw values, zero padded, and for nraw == 5 column 5 = the relative focal length of the general vertical FoV 90 raw2 with centre (raw3, raw4).  nraw <= 8. */
+int pf_op_paramnet_scalars(int device, const float* d_raw, int B, int nraw, int mode, float* d_out8, void* stream);
+/* The conv whose epilogue applies a regression prediction head, in the form conv_fuse_conv1 runs without the fused x2 up-sampling: 3x3 / stride 1 / pad 1,
+ * Cin (a multiple of 32) -> 32 channels, act, then head_kind 1: F.normalize(32 -> 2) into head_out (B, 2, H W) and floats 0-1 of each pn row; head_kind 2:
+ * clamp(32 -> 1, -1, 1) into head_out (B, H W) and (lat, 0) into floats 2-3 of each pn row (pn (B H W, 4) or NULL; the other half of a row is not touched).
+ * The 32-channel map is never stored.  Split-f16 scheme.  tile_id -1: the cost model's tile; a tile id that cannot run this form is PF_ERR_ARG, never replaced --
+ * pf_op_conv2d_head_tile_usable (host only, no device needed) says which can: 1 / 0. */
+int pf_op_conv2d_head_tile_usable(int B, int H, int W, int Cin, int act, int head_kind, int tile_id);
+int pf_op_conv2d_head(int device, const float* d_x, int B, int H, int W, int Cin, const float* h_weight /*[32][Cin][3][3]*/, const float* h_bias /*[32] or NULL*/, int act,
+                      int head_kind, const float* h_head_w /*[nout][32]*/, const float* h_head_b /*[nout]*/, int tile_id, float* d_head_out, float* d_pn /*or NULL*/,
+                      void* stream);
 
 #ifdef __cplusplus
 }

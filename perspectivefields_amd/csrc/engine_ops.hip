@@ -728,4 +728,157 @@ int pf_op_merge_bf16(int device, const uint16_t* planes, long plane_elems, long 
   return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
 }
 
+// ---- the kernels at the two ends of the forward (elem.hip) and the fused prediction-head epilogue (igemm_common.h), one entry each.  Device buffers are the caller's;
+// an argument the kernel cannot take is PF_ERR_ARG before any launch.  Entries without host weights only enqueue; those with host weights upload them and, like the
+// other pf_op_* entries, wait for the stream before they free the copies.
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static int op_arg_error(const char* msg) { g_create_error = msg; return PF_ERR_ARG; }
+static int op_begin(int device) {
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) g_create_error = err;
+  return rc;
+}
+static bool finite_nonzero3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]) && v[0] != 0.f && v[1] != 0.f && v[2] != 0.f; }
+
+int pf_op_prep_u8(int device, const uint8_t* x, int B, int H, int W, const float* mean3, const float* std3, float* y, void* stream) {
+  if (!x || !y || !mean3 || !std3 || B < 1 || H < 1 || W < 1 || !aligned16(y) || !finite_nonzero3(std3)) return op_arg_error("pf_op_prep_u8: x, y (16-byte aligned), mean3, std3 (non-zero) required; B, H, W >= 1");
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  launch_prep_u8(x, y, (long)B * H * W, mean3, std3, static_cast<hipStream_t>(stream));
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+}
+
+int pf_op_prep_f32_nchw(int device, const float* x, int B, int H, int W, const float* mean3, const float* std3, float* y, void* stream) {
+  if (!x || !y || !mean3 || !std3 || B < 1 || H < 1 || W < 1 || (long)H * W > 0x7fffffffL || !aligned16(y) || !finite_nonzero3(std3)) return op_arg_error("pf_op_prep_f32_nchw: x, y (16-byte aligned), mean3, std3 (non-zero) required; B, H, W >= 1, H W < 2^31");
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  launch_prep_f32_nchw(x, y, B, H * W, mean3, std3, static_cast<hipStream_t>(stream));
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+}
+
+int pf_op_pred_regression(int device, const float* tg, const float* tl, int B, int HW, const float* wg, const float* bg, const float* wl, const float* bl,
+                          float* pg, float* pl, float* pn, void* stream) {
+  if (!tg || !tl || !wg || !bg || !wl || !bl || !pg || !pl || B < 1 || HW < 1 || !aligned16(tg) || !aligned16(tl) || (pn && !aligned16(pn)))
+    return op_arg_error("pf_op_pred_regression: features (16-byte aligned), both heads' weights and biases, pg, pl required (pn optional, 16-byte aligned); B, HW >= 1");
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TmpDev tmp;
+  const float *dwg = tmp.up(wg, 64), *dbg = tmp.up(bg, 2), *dwl = tmp.up(wl, 32), *dbl = tmp.up(bl, 1);
+  if (!dwg || !dbg || !dwl || !dbl) { g_create_error = "pf_op_pred_regression: hipMalloc failed"; tmp.sync_free(s); return PF_ERR_DEVICE; }
+  launch_pred_regression(tg, tl, dwg, dbg, dwl, dbl, pg, pl, pn, B, HW, s);
+  const int out = hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+  tmp.sync_free(s);
+  return out;
+}
+
+int pf_op_decode_cls(int device, const float* logit_g, int ng, const float* logit_l, int nl, int B, int HW, float* dg, float* dl, void* stream) {
+  if (!logit_g || !logit_l || !dg || !dl || ng < 2 || nl < 1 || B < 1 || HW < 1) return op_arg_error("pf_op_decode_cls: logits and outputs required; ng >= 2, nl >= 1, B, HW >= 1");
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  launch_decode_cls(logit_g, ng, logit_l, nl, dg, dl, B, HW, static_cast<hipStream_t>(stream));
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+}
+
+int pf_op_nearest_nhwc4(int device, const float* x, int B, int H, int W, int Ho, int Wo, float* y, void* stream) {
+  if (!x || !y || x == y || B < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || !aligned16(x) || !aligned16(y)) return op_arg_error("pf_op_nearest_nhwc4: x, y (different buffers, 16-byte aligned) required; all sizes >= 1");
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  launch_nearest_nhwc4(x, y, B, H, W, Ho, Wo, static_cast<hipStream_t>(stream));
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+}
+
+int pf_op_gap_ln_head(int device, const float* x, int B, int HW, int C, const float* gamma, const float* beta, float eps, const float* head_w, const float* head_b, int nout,
+                      float* y, void* stream) {
+  if (!x || !y || !gamma || !beta || !head_w || !head_b || B < 1 || HW < 1 || C < 1 || C > 1024 || nout < 1 || !(eps >= 0.f))
+    return op_arg_error("pf_op_gap_ln_head: all operands required; B, HW, nout >= 1; 1 <= C <= 1024 (the pooled row lives in a fixed LDS array); eps >= 0");
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TmpDev tmp;
+  const float *dg = tmp.up(gamma, C), *db = tmp.up(beta, C), *dw = tmp.up(head_w, (size_t)nout * C), *dhb = tmp.up(head_b, nout);
+  if (!dg || !db || !dw || !dhb) { g_create_error = "pf_op_gap_ln_head: hipMalloc failed"; tmp.sync_free(s); return PF_ERR_DEVICE; }
+  launch_gap_ln_head(x, dg, db, dw, dhb, y, B, HW, C, nout, eps, s);
+  const int out = hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+  tmp.sync_free(s);
+  return out;
+}
+
+int pf_op_paramnet_scalars(int device, const float* raw, int B, int nraw, int mode, float* out8, void* stream) {
+  if (!raw || !out8 || B < 1 || nraw < 1 || nraw > 8 || (mode != 0 && mode != 1) || (mode == 0 && nraw < 4)) return op_arg_error("pf_op_paramnet_scalars: raw, out8 required; B >= 1; 1 <= nraw <= 8; mode 0 (needs nraw >= 4) or 1");
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  launch_paramnet_scalars(raw, nraw, out8, B, mode, static_cast<hipStream_t>(stream));
+  return hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+}
+
+// the conv_fuse_conv1 form without the fused up-sampling: 3x3 / stride 1 / pad 1, Cin -> 32, split-f16 scheme, the 1x1 prediction head in the epilogue (no 32-channel map stored)
+static void conv2d_head_params(ConvParams* p, int B, int H, int W, int Cin, int act, int head_kind) {
+  p->KWC = 3 * Cin; p->KWCp = roundup(p->KWC, 32);
+  p->B = B; p->H = H; p->W = W; p->C1 = Cin; p->C2 = 0; p->KH = p->KW = 3; p->stride = 1; p->pad = 1;
+  p->Cout = 32; p->act = act; p->post_relu = 0; p->nchw_out = 0; p->nterms = NT_F16X3;
+  p->g[0].head_kind = head_kind;
+  p->finish();
+}
+static const char* conv2d_head_shape_error(int B, int H, int W, int Cin, int act, int head_kind) {
+  if (B < 1 || H < 1 || W < 1 || Cin < 32 || Cin % 32 != 0) return "B, H, W >= 1 and Cin a positive multiple of 32 required";
+  if ((long)B * H * W * std::max(Cin, 32) * 4 >= 0x7fffffffL) return "activations of 2 GiB and more are not addressable";
+  if (act != ACT_NONE && act != ACT_RELU && act != ACT_GELU) return "act must be 0 (none), 1 (relu) or 2 (gelu)";
+  if (head_kind != 1 && head_kind != 2) return "head_kind must be 1 (gravity: 32 -> 2, normalise) or 2 (latitude: 32 -> 1, clamp)";
+  return nullptr;
+}
+
+int pf_op_conv2d_head_tile_usable(int B, int H, int W, int Cin, int act, int head_kind, int tile_id) {
+  if (conv2d_head_shape_error(B, H, W, Cin, act, head_kind)) return 0;
+  static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};  // the usability rules look at which operands exist, never at their contents
+  static const unsigned short dummy16[2] = {0, 0};
+  ConvParams p;
+  conv2d_head_params(&p, B, H, W, Cin, act, head_kind);
+  p.g[0].x = dummy; p.g[0].w = dummy; p.g[0].w_sb = dummy16; p.g[0].w_h16 = dummy16; p.g[0].w_h16_inv_scale = dummy; p.g[0].bias = dummy;
+  return conv_tile_usable(p, tile_id) ? 1 : 0;
+}
+
+int pf_op_conv2d_head(int device, const float* x, int B, int H, int W, int Cin, const float* hw, const float* hb, int act, int head_kind, const float* head_w, const float* head_b,
+                      int tile_id, float* head_out, float* pn, void* stream) {
+  if (const char* e = conv2d_head_shape_error(B, H, W, Cin, act, head_kind)) { g_create_error = std::string("pf_op_conv2d_head: ") + e; return PF_ERR_ARG; }
+  if (!x || !hw || !head_w || !head_b || !head_out || !aligned16(x) || (pn && !aligned16(pn))) return op_arg_error("pf_op_conv2d_head: x (16-byte aligned), weight, head_w, head_b, head_out required (pn optional, 16-byte aligned)");
+  if (tile_id < -1 || tile_id >= conv_num_tiles()) return op_arg_error("pf_op_conv2d_head: tile_id must be -1 (automatic) or a tile id");
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TmpDev tmp;
+  ConvParams p;
+  const int nout = head_kind == 1 ? 2 : 1;
+  {
+    int kwc = 0, kwcp = 0;
+    const std::vector<float> packed = pack_conv(hw, 32, Cin, 3, 3, Cin, nullptr, &kwc, &kwcp);
+    const std::vector<unsigned short> sb = split_bf16x3(packed);
+    const F16Planes f = split_f16x2(packed, 32);
+    conv2d_head_params(&p, B, H, W, Cin, act, head_kind);
+    p.g[0].w = tmp.up(packed); p.g[0].w_sb = tmp.up_u16(sb);
+    p.g[0].w_h16 = tmp.up_u16(f.planes); p.g[0].w_h16_inv_scale = tmp.up(f.inv_scale);
+  }
+  p.g[0].bias = tmp.up(hb, 32);
+  p.g[0].x = x;
+  p.g[0].head_w = tmp.up(head_w, (size_t)nout * 32); p.g[0].head_b = tmp.up(head_b, nout);
+  p.g[0].head_out = head_out; p.g[0].head_pn = pn;
+  p.wino_half = conv_wino_half_env();
+  p.sat = t_op_sat; p.sat_limit = t_op_sat_limit;
+  if (!p.g[0].w || !p.g[0].w_sb || !p.g[0].w_h16 || !p.g[0].w_h16_inv_scale || (hb && !p.g[0].bias) || !p.g[0].head_w || !p.g[0].head_b) {
+    g_create_error = "pf_op_conv2d_head: hipMalloc failed"; tmp.sync_free(s); return PF_ERR_DEVICE;
+  }
+  // unlike pf_op_conv2d, a named tile that cannot run this form is an error: a caller that names a tile has run that tile
+  if (tile_id >= 0 && !conv_tile_usable(p, tile_id)) {
+    g_create_error = fmt("pf_op_conv2d_head: tile %d (%s) cannot run the fused prediction head", tile_id, conv_tile_name(tile_id));
+    tmp.sync_free(s);
+    return PF_ERR_ARG;
+  }
+  if (tile_id < 0 && !conv_tile_usable(p, conv_default_tile(p))) { g_create_error = "pf_op_conv2d_head: no tile runs this shape"; tmp.sync_free(s); return PF_ERR_ARG; }
+  launch_conv_tile(p, tile_id, s);
+  const int out = hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+  tmp.sync_free(s);
+  return out;
+}
+
 }  // extern "C"

@@ -118,6 +118,15 @@ _SIGNATURES = {
     "pf_op_upsample2x": (_c.c_int, [_c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _c.c_long, _P]),
     "pf_op_num_conv_tiles": (_c.c_int, []),
     "pf_op_conv_tile_name": (_c.c_char_p, [_c.c_int]),
+    "pf_op_prep_u8": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
+    "pf_op_prep_f32_nchw": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
+    "pf_op_pred_regression": (_c.c_int, [_c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pf_op_decode_cls": (_c.c_int, [_c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
+    "pf_op_nearest_nhwc4": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
+    "pf_op_gap_ln_head": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_float, _P, _P, _c.c_int, _P, _P]),
+    "pf_op_paramnet_scalars": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
+    "pf_op_conv2d_head_tile_usable": (_c.c_int, [_c.c_int] * 7),
+    "pf_op_conv2d_head": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -372,6 +372,124 @@ def conv_tiles():
     return [lib.pf_op_conv_tile_name(i).decode() for i in range(lib.pf_op_num_conv_tiles())]
 
 
+# ---- the kernels at the two ends of the forward (pf_op_prep_* ... pf_op_conv2d_head in include/pf_hip.h)
+def prep_u8(x_u8, mean3, std3):
+    """(B,H,W,3) uint8 -> (B,H,W,4) fp32: (x - mean) / std, channel 3 = 0."""
+    import torch
+
+    lib = load_library()
+    x_u8 = x_u8.contiguous()
+    B, H, W, _ = x_u8.shape
+    m, s = _np(mean3), _np(std3)
+    y = torch.empty((B, H, W, 4), dtype=torch.float32, device=x_u8.device)
+    _check(lib.pf_op_prep_u8(x_u8.device.index, x_u8.data_ptr(), B, H, W, _hp(m), _hp(s), y.data_ptr(), _stream_ptr()), None, "pf_op_prep_u8")
+    return y
+
+
+def prep_f32_nchw(x, mean3, std3):
+    """(B,3,H,W) fp32 -> (B,H,W,4) fp32: (x - mean) / std, channel 3 = 0."""
+    import torch
+
+    lib = load_library()
+    x = x.contiguous()
+    B, _, H, W = x.shape
+    m, s = _np(mean3), _np(std3)
+    y = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
+    _check(lib.pf_op_prep_f32_nchw(x.device.index, x.data_ptr(), B, H, W, _hp(m), _hp(s), y.data_ptr(), _stream_ptr()), None, "pf_op_prep_f32_nchw")
+    return y
+
+
+def pred_regression(tg, tl, wg, bg, wl, bl, with_pn=True, pn_fill=None):
+    """tg, tl: (B,HW,32) -> pg (B,2,HW) normalised, pl (B,HW) clamped, pn (B*HW,4) = (g0, g1, lat, 0) or None."""
+    import torch
+
+    lib = load_library()
+    tg, tl = tg.contiguous(), tl.contiguous()
+    B, HW, _ = tg.shape
+    a = [_np(t) for t in (wg, bg, wl, bl)]
+    pg = torch.empty((B, 2, HW), dtype=torch.float32, device=tg.device)
+    pl = torch.empty((B, HW), dtype=torch.float32, device=tg.device)
+    pn = torch.full((B * HW, 4), float("nan") if pn_fill is None else pn_fill, dtype=torch.float32, device=tg.device) if with_pn else None
+    _check(lib.pf_op_pred_regression(tg.device.index, tg.data_ptr(), tl.data_ptr(), B, HW, _hp(a[0]), _hp(a[1]), _hp(a[2]), _hp(a[3]), pg.data_ptr(), pl.data_ptr(), _dp(pn),
+                                     _stream_ptr()), None, "pf_op_pred_regression")
+    return pg, pl, pn
+
+
+def decode_cls(logit_g, logit_l):
+    """logits (B,ng,HW), (B,nl,HW) -> dg (B,2,HW) unit vectors ((0,0) for the last gravity bin), dl (B,HW) degrees."""
+    import torch
+
+    lib = load_library()
+    logit_g, logit_l = logit_g.contiguous(), logit_l.contiguous()
+    B, ng, HW = logit_g.shape
+    nl = logit_l.shape[1]
+    dg = torch.empty((B, 2, HW), dtype=torch.float32, device=logit_g.device)
+    dl = torch.empty((B, HW), dtype=torch.float32, device=logit_g.device)
+    _check(lib.pf_op_decode_cls(logit_g.device.index, logit_g.data_ptr(), ng, logit_l.data_ptr(), nl, B, HW, dg.data_ptr(), dl.data_ptr(), _stream_ptr()), None, "pf_op_decode_cls")
+    return dg, dl
+
+
+def nearest_nhwc4(x, Ho, Wo):
+    """(B,H,W,4) -> (B,Ho,Wo,4), F.interpolate's default 'nearest'."""
+    import torch
+
+    lib = load_library()
+    x = x.contiguous()
+    B, H, W, _ = x.shape
+    y = torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=x.device)
+    _check(lib.pf_op_nearest_nhwc4(x.device.index, x.data_ptr(), B, H, W, Ho, Wo, y.data_ptr(), _stream_ptr()), None, "pf_op_nearest_nhwc4")
+    return y
+
+
+def gap_ln_head(x, gamma, beta, eps, head_w, head_b):
+    """x: (B,HW,C) -> (B,nout): mean over HW, LayerNorm, Linear."""
+    import torch
+
+    lib = load_library()
+    x = x.contiguous()
+    B, HW, C = x.shape
+    g, b, w, hb = (_np(t) for t in (gamma, beta, head_w, head_b))
+    nout = w.shape[0]
+    y = torch.empty((B, nout), dtype=torch.float32, device=x.device)
+    _check(lib.pf_op_gap_ln_head(x.device.index, x.data_ptr(), B, HW, C, _hp(g), _hp(b), float(eps), _hp(w), _hp(hb), nout, y.data_ptr(), _stream_ptr()), None, "pf_op_gap_ln_head")
+    return y
+
+
+def paramnet_scalars(raw, mode):
+    """raw: (B,nraw) -> (B,8) (pf_op_paramnet_scalars)."""
+    import torch
+
+    lib = load_library()
+    raw = raw.contiguous()
+    B, nraw = raw.shape
+    out = torch.full((B, 8), float("nan"), dtype=torch.float32, device=raw.device)
+    _check(lib.pf_op_paramnet_scalars(raw.device.index, raw.data_ptr(), B, nraw, int(mode), out.data_ptr(), _stream_ptr()), None, "pf_op_paramnet_scalars")
+    return out
+
+
+def conv2d_head_tiles(B, H, W, Cin, act, head_kind):
+    """ids of the conv tiles that can run pf_op_conv2d_head's form (host logic only: no GPU needed)."""
+    lib = load_library()
+    return [t for t in range(lib.pf_op_num_conv_tiles()) if lib.pf_op_conv2d_head_tile_usable(B, H, W, Cin, act, head_kind, t)]
+
+
+def conv2d_head(x, weight, bias, act, head_kind, head_w, head_b, tile=-1, pn=None):
+    """3x3 / stride 1 / pad 1 conv to 32 channels with the prediction head in its epilogue.  x: (B,H,W,Cin) -> head_out (B,2,H*W) (head_kind 1) or (B,H*W) (head_kind 2);
+    pn: optional (B*H*W,4) tensor, partly written in place (head_kind 1: floats 0-1, head_kind 2: floats 2-3 of each row).  A tile that cannot run the form raises."""
+    import torch
+
+    lib = load_library()
+    x = x.contiguous()
+    B, H, W, Cin = x.shape
+    w, b, hw, hb = _np(weight), _np(bias), _np(head_w), _np(head_b)
+    if w.shape != (32, Cin, 3, 3):
+        raise PfError(f"weight shape {w.shape} != (32, {Cin}, 3, 3)")
+    out = torch.empty((B, 2, H * W) if head_kind == 1 else (B, H * W), dtype=torch.float32, device=x.device)
+    _check(lib.pf_op_conv2d_head(x.device.index, x.data_ptr(), B, H, W, Cin, _hp(w), _hp(b), int(act), int(head_kind), _hp(hw), _hp(hb), int(tile), out.data_ptr(), _dp(pn),
+                                 _stream_ptr()), None, "pf_op_conv2d_head")
+    return out
+
+
 def conv2d_bench(B, H, W, Cin, Cout, K, stride=1, pad=0, tile=-1, iters=10, device=0, fmt=0, precision=0):
     """Average ms per launch of one conv shape on random data (tuning aid).  fmt 0: fp32 in / out; 1: split-plane
     input; 2: split-plane input and output (the exact bf16 split).  precision: PF_PRECISION_* of the split tiles

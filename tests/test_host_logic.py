@@ -678,3 +678,23 @@ def test_workspace_dry_run_for_every_batch_and_configuration(monkeypatch):
     finally:
         for _, _, h in engines:
             lib.pf_destroy(h)
+
+
+def test_fused_head_tile_list_is_host_logic():
+    """pf_op_conv2d_head_tile_usable needs no device: tests/test_gpu_head_tail.py reads the tiles of the fused prediction head at collection.  The form runs on the
+    BN = 32 split tiles only -- linear and halo ones -- for both head kinds; an exact-fp32 tile, a wider tile, a Winograd tile and a bad shape are refused."""
+    from perspectivefields_amd import ops
+
+    names = ops.conv_tiles()
+    for kind in (1, 2):
+        tiles = [names[t] for t in ops.conv2d_head_tiles(2, 17, 24, 64, 1, kind)]
+        assert tiles and all(n.endswith(("x32", "x32f2")) for n in tiles), tiles
+        assert any(n.startswith("sbh") for n in tiles) and any(n.startswith("sb") and not n.startswith("sbh") for n in tiles), tiles
+    lib = ops.load_library()
+    for bad in ("128x128p", "128x32p", "sb128x128", "sbh128x64", "wino256x64c"):
+        assert lib.pf_op_conv2d_head_tile_usable(2, 17, 24, 64, 1, 1, names.index(bad)) == 0, bad
+    ok = names.index("sb128x32")
+    assert lib.pf_op_conv2d_head_tile_usable(2, 17, 24, 64, 1, 1, ok) == 1
+    for args in ((0, 17, 24, 64, 1, 1), (2, 17, 24, 48, 1, 1), (2, 17, 24, 64, 3, 1), (2, 17, 24, 64, 1, 0), (2, 17, 24, 64, 1, 3), (81, 320, 320, 256, 1, 1)):
+        assert lib.pf_op_conv2d_head_tile_usable(*args, ok) == 0, args
+    assert lib.pf_op_conv2d_head_tile_usable(2, 17, 24, 64, 1, 1, -1) == 0 and lib.pf_op_conv2d_head_tile_usable(2, 17, 24, 64, 1, 1, len(names)) == 0
