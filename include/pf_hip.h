@@ -520,6 +520,37 @@ int pf_pano_rotate(int device, int n_pano, const void* const* h_pano, const int3
 int pf_pano_fields(int device, int batch, const float* d_rot3 /*[batch][3]*/, int inverse, int H, int W, float* d_up /*[batch][2][H][W]*/,
                    float* d_lat /*[batch][H][W]*/, void* stream);
 
+/* Antialiased forms of pf_pano_crop, pf_reproject and pf_pano_rotate by supersampling (gather_ss.hip): the argument list of the
+ * parent with `samples` = S, an integer in 1 ... PF_GATHER_MAX_SAMPLES, before `stream`.  Every output pixel is the mean of S x S sub-samples, and
+ * each sub-sample is the parent's per-sample model, unchanged:
+ *   point       sub-sample (i, j), i, j in [0, S), of output pixel (row, col) sits at (a, b) = (col + (j + 1/2)/S, row + (i + 1/2)/S), which replaces
+ *               (col + 1/2, row + 1/2) in the parent's model (for pf_pano_rotate: in lon and lat).  Ray, validity, source coordinate, tap rule and
+ *               blend order stay the parent's.  Because F = f*H and Cx = (cx + 1/2)*W scale with the size, sub-sample (i, j) of pixel (row, col) is
+ *               the pixel centre (S row + i, S col + j) of the same call at the output size (S H, S W): the S x S block mean of that call
+ *   image       the fp32 sum of the valid sub-samples' bilinear values, i-major then j, divided by their count n as sum / (float)n; S = 1 gives the
+ *               parent's bits.  PF_PANO_U8: that value rounded half up, clamped to [0, 255].  A sub-sample is valid where the parent's pixel is: it
+ *               has a ray (pf_pano_crop), it is valid in pf_reproject's step 5, always for pf_pano_rotate with finite angles
+ *   empty       a pixel with no valid sub-sample is 0 for pf_pano_crop_ss and pf_pano_rotate_ss, `fill` for pf_reproject_ss.  Non-finite parameters
+ *               behave as in the parent: 0 or `fill`, NaN labels, no load issued
+ *   mask        pf_reproject_ss: 1 iff at least one sub-sample is valid, so mask = 0 <=> the pixel holds `fill`
+ *   map         pf_reproject_ss: the pixel centre's (a_s, b_s), the bits of pf_reproject.  With an even S the centre is not itself a sub-sample, so
+ *               the map may be finite and inside the source where the mask is 0, and the other way round, next to a border
+ *   labels      pf_pano_crop_ss, pf_pano_rotate_ss: bit-identical to the parent's.  They describe the pixel, not its footprint
+ * S <= 4 with bilinear taps covers minifications up to about 8x.  Sizes, pointers, the parent's argument checks and launches are the parent's;
+ * `samples` outside 1 ... PF_GATHER_MAX_SAMPLES returns PF_ERR_ARG before any device work, with a message that begins with the function's name and
+ * names `samples`.  Deterministic, each output's bits independent of the batch it is in.  pf_pano_compose and pf_yaw_moments (several views per
+ * pixel, weights of their own) have no such form. */
+#define PF_GATHER_MAX_SAMPLES 4
+int pf_pano_crop_ss(int device, int n_pano, const void* const* h_pano, const int32_t* h_pano_hw /*[n_pano][2]*/, int dtype, int batch,
+                    const int32_t* h_pano_index /*[batch]*/, const float* d_cam7 /*[batch][7]*/, int H, int W,
+                    void* d_img /*[batch][H][W][3], dtype*/, float* d_up /*[batch][2][H][W]*/, float* d_lat /*[batch][H][W]*/, int samples, void* stream);
+int pf_reproject_ss(int device, int n_src, const void* const* h_src, const int32_t* h_src_hw /*[n_src][2]*/, int dtype /*PF_PANO_U8|PF_PANO_F32*/,
+                    int batch, const int32_t* h_src_index /*[batch]*/, const float* d_cam_src7 /*[batch][7]*/, const float* d_cam_dst7 /*[batch][7]*/,
+                    int H, int W, float fill, void* d_img, uint8_t* d_valid /*or NULL*/, float* d_map /*or NULL*/, int samples, void* stream);
+int pf_pano_rotate_ss(int device, int n_pano, const void* const* h_pano, const int32_t* h_pano_hw /*[n_pano][2]*/, int dtype, int batch,
+                      const int32_t* h_pano_index /*[batch]*/, const float* d_rot3 /*[batch][3] roll, pitch, yaw, radians*/, int inverse, int H, int W,
+                      void* d_img /*[batch][H][W][3], dtype*/, float* d_up /*[batch][2][H][W]*/, float* d_lat /*[batch][H][W]*/, int samples, void* stream);
+
 /* The relative yaw of camera views of one centre, from the pictures: for ordered pairs (a, b) of views and a list of candidate turns, the moments of
  * the two luminance images on their overlap, from which the zero-mean normalised cross-correlation follows (yaw_align.hip).
  * The fields give roll, pitch and intrinsics of a view but not the direction it faces; with those known, two views of one centre differ by a single

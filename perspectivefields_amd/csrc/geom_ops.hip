@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -108,6 +108,64 @@ int pf_pano_rotate(int device, int n_pano, const void* const* pano, const int32_
   return gather_run(kind, launch_pano_rotate, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_rot3 != nullptr, H, W, d_img,
                     !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr, misalign(d_up, 15) | misalign(d_lat, 15), stream,
                     [=](PanoRotBatch& rb, int i0) {
+                      rb.inverse = inverse ? 1 : 0;
+                      rb.rot = d_rot3 + (size_t)i0 * 3;
+                      rb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
+                      rb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
+                    });
+}
+
+// The supersampled forms (gather_ss.hip): `samples` is checked first, then the parent's checks in the parent's order under the new name
+static bool samples_ok(const char* name, int samples) {
+  if (samples >= 1 && samples <= PF_GATHER_MAX_SAMPLES) return true;
+  g_create_error = fmt("%s: samples %d, must be in [1, %d]", name, samples, PF_GATHER_MAX_SAMPLES);
+  return false;
+}
+
+int pf_pano_crop_ss(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
+                    const float* d_cam7, int H, int W, void* d_img, float* d_up, float* d_lat, int samples, void* stream) {
+  static const GatherKind kind{"pf_pano_crop_ss", "panorama", "crop", 2, "needs at least one panorama (h_pano, h_pano_hw)",
+                               "batch >= 1, h_pano_index, d_cam7 and d_img are required"};
+  if (!samples_ok(kind.name, samples)) return PF_ERR_ARG;
+  const size_t npx = (size_t)H * W;
+  return gather_run(kind, launch_pano_crop_ss, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_cam7 != nullptr, H, W, d_img,
+                    !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr, misalign(d_up, 15) | misalign(d_lat, 15), stream,
+                    [=](PanoSsBatch& pb, int i0) {
+                      pb.samples = samples;
+                      pb.cam = d_cam7 + (size_t)i0 * 7;
+                      pb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
+                      pb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
+                    });
+}
+
+int pf_reproject_ss(int device, int n_src, const void* const* src, const int32_t* src_hw, int dtype, int B, const int32_t* src_index,
+                    const float* d_cam_src7, const float* d_cam_dst7, int H, int W, float fill, void* d_img, uint8_t* d_valid, float* d_map, int samples,
+                    void* stream) {
+  static const GatherKind kind{"pf_reproject_ss", "source", "output", 1, "needs at least one source image (h_src, h_src_hw)",
+                               "batch >= 1, h_src_index, d_cam_src7, d_cam_dst7 and d_img are required"};
+  if (!samples_ok(kind.name, samples)) return PF_ERR_ARG;
+  const size_t npx = (size_t)H * W;
+  return gather_run(kind, launch_reproject_ss, device, n_src, src, src_hw, dtype, B, src_index, d_cam_src7 && d_cam_dst7, H, W, d_img, nullptr,
+                    misalign(d_valid, 3) | misalign(d_map, 15), stream, [=](ReprojSsBatch& rb, int i0) {
+                      rb.samples = samples;
+                      rb.fill = fill;
+                      rb.cam_src = d_cam_src7 + (size_t)i0 * 7;
+                      rb.cam_dst = d_cam_dst7 + (size_t)i0 * 7;
+                      rb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
+                      rb.map = d_map ? d_map + (size_t)i0 * 2 * npx : nullptr;
+                    });
+}
+
+int pf_pano_rotate_ss(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
+                      const float* d_rot3, int inverse, int H, int W, void* d_img, float* d_up, float* d_lat, int samples, void* stream) {
+  static const GatherKind kind{"pf_pano_rotate_ss", "panorama", "output", 2, "needs at least one panorama (h_pano, h_pano_hw)",
+                               "batch >= 1, h_pano_index, d_rot3 and d_img are required"};
+  if (!samples_ok(kind.name, samples)) return PF_ERR_ARG;
+  const size_t npx = (size_t)H * W;
+  return gather_run(kind, launch_pano_rotate_ss, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_rot3 != nullptr, H, W, d_img,
+                    !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr, misalign(d_up, 15) | misalign(d_lat, 15), stream,
+                    [=](PanoRotSsBatch& rb, int i0) {
+                      rb.samples = samples;
                       rb.inverse = inverse ? 1 : 0;
                       rb.rot = d_rot3 + (size_t)i0 * 3;
                       rb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;

@@ -508,6 +508,49 @@ struct PanoFieldsBatch {
 };
 void launch_pano_fields(const PanoFieldsBatch& fb, hipStream_t s);
 
+// The supersampled forms of the three one-source gathers (gather_ss.hip, include/pf_hip.h pf_pano_crop_ss / pf_reproject_ss / pf_pano_rotate_ss):
+// every output pixel is the mean of the valid ones of samples x samples sub-samples.  Arguments of their own, so that the layouts above stay as they
+// were measured: the launch's shape, `samples` in the word behind it, the sources at offset 32, then what the parent's struct holds
+struct PanoSsBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int samples;        // S in [1, PF_GATHER_MAX_SAMPLES]
+  GatherSources src;  // the panoramas (Hp, Wp, 3)
+  const float* cam;   // [n][7], as PanoBatch
+  void* img;
+  float* up;
+  float* lat;
+};
+void launch_pano_crop_ss(const PanoSsBatch& pb, int dtype, hipStream_t s);
+struct ReprojSsBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int samples;
+  GatherSources src;  // (Hs, Ws, 3)
+  float fill;
+  const float* cam_src;  // [n][7], as ReprojBatch
+  const float* cam_dst;
+  void* img;
+  uint8_t* valid;  // NULL or [n][H][W]: 1 where a sub-sample is valid
+  float* map;      // NULL or [n][2][H][W]: (a_s, b_s) of the pixel centre
+};
+void launch_reproject_ss(const ReprojSsBatch& rb, int dtype, hipStream_t s);
+struct PanoRotSsBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int samples;
+  GatherSources src;  // the source panoramas (Hs, Ws, 3)
+  int inverse;
+  const float* rot;  // [n][3], as PanoRotBatch
+  void* img;
+  float* up;
+  float* lat;
+};
+void launch_pano_rotate_ss(const PanoRotSsBatch& rb, int dtype, hipStream_t s);
+static_assert(offsetof(PanoSsBatch, samples) == 28 && offsetof(PanoSsBatch, src) == 32, "PanoSsBatch layout");
+static_assert(offsetof(ReprojSsBatch, samples) == 28 && offsetof(ReprojSsBatch, src) == 32, "ReprojSsBatch layout");
+static_assert(offsetof(PanoRotSsBatch, samples) == 28 && offsetof(PanoRotSsBatch, src) == 32, "PanoRotSsBatch layout");
+
 // camera views of one centre -> equirectangular panoramas (pano_compose.hip, include/pf_hip.h pf_pano_compose): the outputs of a launch are up to MAX
 // panoramas, its sources up to MAX views; panorama k blends the views [first[k], first[k] + count[k]) of the launch in that order
 struct ComposeBatch {

@@ -544,7 +544,7 @@ class PerspectiveFields(nn.Module):
 
     def rectify(self, images, preds, *, level="roll", undistort=True, rel_focal=None, height=None, width=None, **kw):
         """The images warped with their recovered cameras, on the GPU (see reproject_image for `images`, the other options --
-        src_index, fill, return_valid, return_map -- and what is returned).  preds: one result dict, or a list of them, of inference*
+        src_index, fill, return_valid, return_map, samples -- and what is returned).  preds: one result dict, or a list of them, of inference*
         (a ParamNet model) or of fit_camera; the source camera is pred_roll, pred_pitch, pred_rel_focal, pred_rel_cx, pred_rel_cy and
         pred_xi (absent keys count as 0), one per image (or per src_index entry).
         level: "roll" -- the destination camera has roll 0 and the source's pitch (an upright view); "full" -- roll 0 and pitch 0 (the
@@ -581,7 +581,7 @@ class PerspectiveFields(nn.Module):
             raise ValueError("align_yaw takes the angles of its preds, which are degrees: no mode")
         return align_yaw(images, PerspectiveFields._pred_cameras("align_yaw", preds), mode="deg", **kw)
 
-    def level_panorama(self, pano, *, n_yaw=8, view_pitch=(0.0,), vfov=90.0, view_size=None, use="paramnet", return_info=False, preds=None):
+    def level_panorama(self, pano, *, n_yaw=8, view_pitch=(0.0,), vfov=90.0, view_size=None, use="paramnet", return_info=False, preds=None, samples=1):
         """A tilted equirectangular panorama made upright, on the GPU: n_yaw x len(view_pitch) square pinhole views of `vfov` degrees are cut out of it
         (crop_panorama: yaw k 360 / n_yaw, the pitches of view_pitch in degrees, roll 0, view_size pixels, default the network's input size), the model
         predicts every view's roll and pitch, `gravity_from_views` turns them into the panorama's roll and pitch, and
@@ -589,12 +589,14 @@ class PerspectiveFields(nn.Module):
         pano: one CUDA tensor (H, W, 3), uint8 or float32 (on the 0 .. 255 scale; the views go to the network as uint8).
         use: "paramnet" -- the ParamNet scalars pred_roll / pred_pitch of every view; "fit" -- `fit_camera` on every view's dense fields (the only
         choice for a PersNet model).
+        samples: the antialiasing of both steps, 1 .. 4 (crop_panorama's and rotate_panorama's `samples`); the views shrink a large panorama a lot.
         preds: the per-view results, one dict per view in the order pitch-major, yaw-minor -- inference results, or dicts with pred_roll / pred_pitch
         ("paramnet") or pred_gravity_original / pred_latitude_original ("fit"); given, nothing is cropped and the network does not run.
         Returns the upright panorama (H, W, 3) in the source's dtype; with return_info=True also a dict: roll, pitch (the estimate, degrees), views
         (the views' roll, pitch, yaw), preds (one per view, after the fit with use="fit") and gravity (gravity_from_views' result)."""
         if use not in ("paramnet", "fit"):
             raise ValueError("use must be 'paramnet' or 'fit'")
+        samples = _check_samples("level_panorama", samples)
         n_yaw = operator.index(n_yaw)
         pitches = [float(v) for v in (view_pitch if isinstance(view_pitch, (list, tuple)) else [view_pitch])]
         if n_yaw < 1 or not pitches:
@@ -611,7 +613,8 @@ class PerspectiveFields(nn.Module):
                  "yaw": [k * 360.0 / n_yaw for _ in pitches for k in range(n_yaw)]}
         n = n_yaw * len(pitches)
         if preds is None:
-            crops = crop_panorama(pano, 0.0, views["pitch"], 0.5 / math.tan(math.radians(float(vfov)) / 2), yaw=views["yaw"], height=size, width=size, fields=False)[0]
+            crops = crop_panorama(pano, 0.0, views["pitch"], 0.5 / math.tan(math.radians(float(vfov)) / 2), yaw=views["yaw"], height=size, width=size, fields=False,
+                                  samples=samples)[0]
             if crops.dtype != torch.uint8:
                 crops = crops.round().clamp(0, 255).to(torch.uint8)
             preds = self.inference_batch(list(crops))
@@ -623,7 +626,7 @@ class PerspectiveFields(nn.Module):
             preds = self.fit_camera(preds)
         cams = PerspectiveFields._pred_cameras("level_panorama", preds)
         est = gravity_from_views(views, cams["roll"], cams["pitch"], mode="deg")
-        out = rotate_panorama(pano, est["roll"], est["pitch"], inverse=True, mode="deg")[0]
+        out = rotate_panorama(pano, est["roll"], est["pitch"], inverse=True, mode="deg", samples=samples)[0]
         if not return_info:
             return out
         return out, {"roll": est["roll"], "pitch": est["pitch"], "views": views, "preds": preds, "gravity": est}
@@ -1342,6 +1345,16 @@ def _camera_rows(ts, angles, B, dev, mode):
     return torch.stack([t.expand(B) for t in ts], 1).to(torch.float32)
 
 
+GATHER_MAX_SAMPLES = 4   # include/pf_hip.h PF_GATHER_MAX_SAMPLES
+
+
+def _check_samples(fn, samples):
+    """`samples` of a gather: an int in 1 .. GATHER_MAX_SAMPLES (the side of the grid of sub-samples per output pixel)"""
+    if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or not 1 <= samples <= GATHER_MAX_SAMPLES:
+        raise ValueError(f"{fn}: samples must be an integer in [1, {GATHER_MAX_SAMPLES}]; got {samples!r}")
+    return int(samples)
+
+
 def _source_arrays(srcs, sizes, idx):
     """the ctypes arguments that name a gather's sources: their pointers, their (H, W) pairs, the source of each output"""
     n = len(srcs)
@@ -1349,7 +1362,7 @@ def _source_arrays(srcs, sizes, idx):
             (ctypes.c_int32 * len(idx))(*idx))
 
 
-def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0.0, xi=0.0, height, width, pano_index=None, mode="deg", fields=True):
+def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0.0, xi=0.0, height, width, pano_index=None, mode="deg", fields=True, samples=1):
     """Equirectangular panoramas -> camera views and their ground-truth perspective fields on the GPU: the reference's labelled-data
     tooling (PanoCam.get_image / crop_equi, crop_distortion for the Unified Spherical Model, get_up_general / get_lat_general in
     utils/panocam.py).  Camera model, sampling and labels: include/pf_hip.h pf_pano_crop.
@@ -1364,12 +1377,15 @@ def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0
 
     The orientation conventions are those of `fields_from_params` (pinned to the reference by tests/golden): x right, y down,
     positive pitch looks up, positive yaw turns towards higher panorama columns, row 0 of the panorama is the north pole and its
-    centre column is longitude 0.  Pixel parity with the reference's equilib backend is not checked.  The reference's
+    centre column is longitude 0.  samples=S (1 .. 4) antialiases a crop that minifies its panorama: every pixel is the mean of S x S bilinear
+    sub-samples (include/pf_hip.h pf_pano_crop_ss); the labels do not depend on it, and S = 1 is the one sample at the pixel centre.
+    Pixel parity with the reference's equilib backend is not checked.  The reference's
     get_image(vfov, im_w, im_h, azimuth, elevation, roll, ar) maps to height=im_h, width=im_w, yaw=azimuth, pitch=elevation, roll=roll,
     rel_focal = 0.5 / tan(vfov / 2) (a centred crop with square pixels), rel_cx = rel_cy = 0, xi = 0.
     GPU only: CPU panoramas raise PfError."""
     from .engine import _check, _stream_ptr, load_library
 
+    samples = _check_samples("crop_panorama", samples)
     panos, dev = _cuda_image_list("crop_panorama", [pano] if torch.is_tensor(pano) else list(pano), ("panorama", "panoramas"),
                                   "a panorama must be (Hp, Wp, 3) with Hp, Wp >= 2", 2)
     H, W = int(height), int(width)
@@ -1402,8 +1418,12 @@ def crop_panorama(pano, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0
     p_pano, hw, c_idx = _source_arrays(panos, [(int(p.shape[0]), int(p.shape[1])) for p in panos], idx)
     lib = load_library()
     with torch.cuda.device(dev):
-        _check(lib.pf_pano_crop(dev.index, len(panos), p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, cam.data_ptr(), H, W, img.data_ptr(),
-                                up.data_ptr() if fields else None, lat.data_ptr() if fields else None, _stream_ptr()), None, "pf_pano_crop")
+        args = (dev.index, len(panos), p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, cam.data_ptr(), H, W, img.data_ptr(),
+                up.data_ptr() if fields else None, lat.data_ptr() if fields else None)
+        if samples == 1:
+            _check(lib.pf_pano_crop(*args, _stream_ptr()), None, "pf_pano_crop")
+        else:
+            _check(lib.pf_pano_crop_ss(*args, samples, _stream_ptr()), None, "pf_pano_crop_ss")
     return img, up, lat
 
 
@@ -1418,7 +1438,7 @@ def _rotation_params(fn, named):
     return ts
 
 
-def rotate_panorama(pano, roll=0.0, pitch=0.0, yaw=0.0, *, inverse=False, height=None, width=None, pano_index=None, mode="deg", fields=False):
+def rotate_panorama(pano, roll=0.0, pitch=0.0, yaw=0.0, *, inverse=False, height=None, width=None, pano_index=None, mode="deg", fields=False, samples=1):
     """Equirectangular panoramas -> rotated equirectangular panoramas on the GPU, with the perspective fields of the panoramic camera on request:
     levelling a tilted 360 degree picture, tilting an upright one (labelled data for tilted panoramas), re-centring a composite.  Model, sampling and
     labels: include/pf_hip.h pf_pano_rotate; the conventions are `crop_panorama`'s.
@@ -1432,8 +1452,12 @@ def rotate_panorama(pano, roll=0.0, pitch=0.0, yaw=0.0, *, inverse=False, height
     when they differ in size).
     Returns the images (B, H, W, 3) in the panorama's dtype; with fields=True (images, up (B, 2, H, W), lat (B, H, W) degrees), the perspective
     fields of the output's camera in the layout of pred_gravity_original / pred_latitude_original (up is NaN at a pixel centre on the world's zenith
-    or nadir).  Non-finite angles give an image of 0 and NaN fields.  GPU only: CPU panoramas raise PfError."""
+    or nadir).  Non-finite angles give an image of 0 and NaN fields.  samples=S (1 .. 4) antialiases an output smaller than its source: every pixel
+    is the mean of S x S bilinear sub-samples (include/pf_hip.h pf_pano_rotate_ss); the fields do not depend on it.
+    GPU only: CPU panoramas raise PfError."""
     from .engine import _check, _stream_ptr, load_library
+
+    samples = _check_samples("rotate_panorama", samples)
 
     panos, dev = _cuda_image_list("rotate_panorama", [pano] if torch.is_tensor(pano) else list(pano), ("panorama", "panoramas"),
                                   "a panorama must be (Hs, Ws, 3) with Hs, Ws >= 2", 2)
@@ -1470,8 +1494,12 @@ def rotate_panorama(pano, roll=0.0, pitch=0.0, yaw=0.0, *, inverse=False, height
     p_pano, hw, c_idx = _source_arrays(panos, sizes, idx)
     lib = load_library()
     with torch.cuda.device(dev):
-        _check(lib.pf_pano_rotate(dev.index, len(panos), p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, rot.data_ptr(), 1 if inverse else 0, H, W,
-                                  img.data_ptr(), up.data_ptr() if fields else None, lat.data_ptr() if fields else None, _stream_ptr()), None, "pf_pano_rotate")
+        args = (dev.index, len(panos), p_pano, hw, _PANO_DTYPES[panos[0].dtype], B, c_idx, rot.data_ptr(), 1 if inverse else 0, H, W,
+                img.data_ptr(), up.data_ptr() if fields else None, lat.data_ptr() if fields else None)
+        if samples == 1:
+            _check(lib.pf_pano_rotate(*args, _stream_ptr()), None, "pf_pano_rotate")
+        else:
+            _check(lib.pf_pano_rotate_ss(*args, samples, _stream_ptr()), None, "pf_pano_rotate_ss")
     return (img, up, lat) if fields else img
 
 
@@ -1606,7 +1634,7 @@ def _camera_params(what, cam, fn="reproject_image"):
     return ts
 
 
-def reproject_image(images, src, dst, *, height=None, width=None, src_index=None, mode="deg", fill=0, return_valid=False, return_map=False):
+def reproject_image(images, src, dst, *, height=None, width=None, src_index=None, mode="deg", fill=0, return_valid=False, return_map=False, samples=1):
     """Images of one camera -> images of another camera of the same centre on the GPU: upright rectification (destination roll 0, or roll
     and pitch 0), undistortion of a Unified Spherical Model view (destination xi = 0), another focal length, principal point or output
     size, or any other view of the same centre.  Model: include/pf_hip.h pf_reproject; the cameras are those of
@@ -1622,8 +1650,12 @@ def reproject_image(images, src, dst, *, height=None, width=None, src_index=None
     source camera, outside its image).
     Returns the images (B, H, W, 3) in the sources' dtype; with return_valid / return_map a tuple that adds the mask (B, H, W) bool and /
     or the map (B, 2, H, W) float32 of source coordinates (a_s, b_s) in pixel-edge units (NaN where the source camera does not see the ray).
-    Bilinear sampling without antialiasing or mip levels: a strong minification aliases.  GPU only: CPU images raise PfError."""
+    Bilinear sampling without mip levels; samples=S (1 .. 4) antialiases an output that minifies its source: every pixel is the mean of the valid
+    ones of S x S bilinear sub-samples (include/pf_hip.h pf_reproject_ss).  The mask is then True where any sub-sample is valid
+    (the pixels outside it, and only those, were given `fill`), and the map stays the pixel centre's.  GPU only: CPU images raise PfError."""
     from .engine import _check, _stream_ptr, load_library
+
+    samples = _check_samples("reproject_image", samples)
 
     batched = torch.is_tensor(images) and images.dim() == 4   # (B, Hs, Ws, 3): only as one tensor, not inside a list
     srcs = [] if batched and images.shape[0] < 1 else [images] if torch.is_tensor(images) else list(images)
@@ -1667,9 +1699,12 @@ def reproject_image(images, src, dst, *, height=None, width=None, src_index=None
     p_src, hw, c_idx = _source_arrays(srcs, sizes, idx)
     lib = load_library()
     with torch.cuda.device(dev):
-        _check(lib.pf_reproject(dev.index, n, p_src, hw, _PANO_DTYPES[srcs[0].dtype], B, c_idx, cam_s.data_ptr(), cam_d.data_ptr(), H, W, fill,
-                                img.data_ptr(), valid.data_ptr() if return_valid else None, cmap.data_ptr() if return_map else None, _stream_ptr()),
-               None, "pf_reproject")
+        args = (dev.index, n, p_src, hw, _PANO_DTYPES[srcs[0].dtype], B, c_idx, cam_s.data_ptr(), cam_d.data_ptr(), H, W, fill,
+                img.data_ptr(), valid.data_ptr() if return_valid else None, cmap.data_ptr() if return_map else None)
+        if samples == 1:
+            _check(lib.pf_reproject(*args, _stream_ptr()), None, "pf_reproject")
+        else:
+            _check(lib.pf_reproject_ss(*args, samples, _stream_ptr()), None, "pf_reproject_ss")
     out = (img,) + ((valid.view(torch.bool),) if return_valid else ()) + ((cmap,) if return_map else ())
     return out[0] if len(out) == 1 else out
 
