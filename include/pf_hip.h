@@ -621,6 +621,59 @@ int pf_place_scores(int device, int n_bg, const float* const* h_bg_up, const flo
                     const int32_t* h_pairs /*[n_pair][2]: (background, object)*/, int stride, double* d_out /*[pair][P][Q][3]*/, void* d_workspace,
                     size_t workspace_bytes, void* stream);
 
+/* Similarity transform of a perspective field: the fields of a picture that is resized by s and turned by phi in its plane (field_xform.hip, DESIGN.md
+ * section 26).  Field layout and the VALID rule are pf_place_scores'.  A VARIANT is a scale s > 0 and a rotation phi in degrees.
+ *   map        source (h, w) -> output (h', w'): a source point p goes to c_out + s R(phi) (p - c_src), R(phi) = [[cos phi, -sin phi], [sin phi, cos phi]]
+ *              in array coordinates (x right, y down), c_src = (w/2, h/2), c_out = (w'/2, h'/2).  Positive phi turns the picture clockwise on the
+ *              screen: the fields of a camera whose roll is lower by phi.  cos phi and sin phi are taken in fp64 from remainder(phi, 360) and are
+ *              exactly 0 or +-1 at the multiples of 90.
+ *   size       pf_fields_transform_size: h' = max(1, floor(s (h |cos phi| + w |sin phi|) + 1/2)), w' with h and w exchanged, in fp64; PF_ERR_ARG for
+ *              h, w < 1, a scale that is not finite and > 0, a rotation that is not finite, or h' w' >= 2^31.  pf_fields_transform takes any h', w'.
+ *   sampling   output pixel (r', c'): d = (c' + 1/2 - w'/2, r' + 1/2 - h'/2), source position (x, y) = c_src + R(-phi) d / s - (1/2, 1/2) in
+ *              pixel-centre coordinates, computed in fp32 from cos phi, sin phi and 1 / s rounded to fp32.  Four bilinear taps at floor(x), floor(y) and
+ *              their + 1 neighbours; a tap outside the array or on an invalid pixel is DROPPED, not clamped.  W_v = the weights of the taps left.  The
+ *              pixel is valid iff W_v >= 1/2 and the mix m = sum w_k u_k, rounded to fp32, passes the length rule of VALID.
+ *                lat' = sum w_k lat_k / W_v
+ *                up'  = R(phi) m scaled to unit length (the taps are not normalised first); left unscaled where its squared length is within 2^-22
+ *                       of 1 already, so that a vector that is of unit length in fp32 keeps its bits
+ *              both in fp64 from the fp32 weights and rounded to fp32 once.  An invalid pixel is NaN in all three planes.
+ *              So a silhouette keeps its outline to half a pixel, an array border behaves like a clamp, a position more than half a pixel outside the
+ *              source is invalid, and s = 1, phi = 0 at the source's size returns the bits of a field of unit up vectors.
+ *   no prefilter: fields are smooth; only a silhouette aliases when s is far below 1.
+ * Job k transforms source field h_up[k], h_lat[k] of size h_hw[k] by variant h_variants[k] = (s, phi) into h_out_up[k] (2, h', w') and h_out_lat[k]
+ * (h', w') of size h_out_hw[k]; a source may be named by any number of jobs, an output by one.  All h_* are HOST arrays; the fields are DEVICE pointers.
+ * Argument errors (n < 1, NULL arrays or pointers, a side < 1, 2^31 pixels or more on either side, a bad variant) return PF_ERR_ARG before any device
+ * work.  One launch per 32 jobs on `stream`; no atomics, no host-to-device copy, no host synchronisation; stateless, no handle. */
+int pf_fields_transform_size(int h, int w, double scale, double rotation_deg, int32_t* h_out_hw /*[2]*/);
+int pf_fields_transform(int device, int n, const float* const* h_up, const float* const* h_lat, const int32_t* h_hw /*[n][2]*/,
+                        const double* h_variants /*[n][2]: (scale, rotation in degrees)*/, const int32_t* h_out_hw /*[n][2]*/, float* const* h_out_up,
+                        float* const* h_out_lat, void* stream);
+
+/* pf_place_scores over a set of variants of every object, and the best (variant, offset) of every pair found on the device.
+ * Backgrounds, objects, pairs and stride as pf_place_scores takes them; h_variants = HOST [n_var][2] (scale, rotation in degrees), shared by all pairs.
+ *   1. every object is transformed by every variant into the workspace (pf_fields_transform at pf_fields_transform_size's size);
+ *   2. pf_place_scores' three kernels, unchanged, over every (pair, variant) whose transformed object fits its background, 32 per launch.  The raw
+ *      records {S_up, S_lat, n} go to d_maps: pair by pair, variant by variant, P Q 3 doubles each (P, Q from the transformed size), nothing for a
+ *      variant that does not fit.  They are the bits pf_place_scores gives on pf_fields_transform's output;
+ *   3. per (pair, variant) and placement, in fp64: up_mean = S_up / n, lat_mean = S_lat / n, pfd = w_up up_mean + w_lat lat_mean (two products and
+ *      a sum, each rounded), +inf where n < min_valid x (valid pixels of the transformed object) or n = 0.  The lowest pfd per variant, then per pair
+ *      over the variants; ties go to the lowest variant, then to the first placement in row-major order.
+ *   d_var[pair][variant]  = {best pfd, row, col, valid pixels of the variant, h', w'}; a variant that does not fit, or has no finite pfd: +inf, -1, -1
+ *   d_best[pair]          = {pfd, up_mean, lat_mean, n, variant, row, col}; row, col in background pixels; all +inf: {+inf, NaN, NaN, 0, -1, -1, -1}
+ * d_maps holds maps_doubles doubles, at least the sum above; d_maps, d_best, d_var 8-byte aligned.  Argument errors -- pf_place_scores' except that an
+ * object larger than its background is no error here, n_var < 1, a bad variant (pf_fields_transform_size), a transformed object of more than 65535
+ * chunks in a pair it fits, min_valid outside [0, 1], a weight that is negative or not finite, a small d_maps or workspace -- return PF_ERR_ARG before
+ * any device work; pf_place_search_workspace_bytes is 0 for arguments that set the layout and are rejected.  All launches on `stream`, no atomics,
+ * no host-to-device copy, no host synchronisation; every value depends on its pair's fields, the variants, the stride, the threshold and the weights
+ * only: the same bits in any batch of pairs, in any order of them, and on every run.  Stateless, no handle. */
+size_t pf_place_search_workspace_bytes(int n_bg, const int32_t* h_bg_hw /*[n_bg][2]*/, int n_obj, const int32_t* h_obj_hw /*[n_obj][2]*/, int n_pair,
+                                       const int32_t* h_pairs /*[n_pair][2]*/, int n_var, const double* h_variants /*[n_var][2]*/, int stride);
+int pf_place_search(int device, int n_bg, const float* const* h_bg_up, const float* const* h_bg_lat, const int32_t* h_bg_hw /*[n_bg][2]*/, int n_obj,
+                    const float* const* h_obj_up, const float* const* h_obj_lat, const int32_t* h_obj_hw /*[n_obj][2]*/, int n_pair,
+                    const int32_t* h_pairs /*[n_pair][2]: (background, object)*/, int n_var, const double* h_variants /*[n_var][2]*/, int stride,
+                    double min_valid, double w_up, double w_lat, double* d_maps, size_t maps_doubles, double* d_best /*[n_pair][7]*/,
+                    double* d_var /*[n_pair][n_var][6]*/, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Perspective fields drawn over their images on the device: a latitude tint, iso-latitude lines and up arrows (draw_fields.hip, DESIGN.md
  * section 22).  The drawing model is this library's own; parity with a plotting library's rasteriser is not offered.
  * Per image: the picture img [H][W][3] (channel-interleaved, uint8 or fp32, values on the 0 - 255 scale in both types: the colours below are given on

@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -471,6 +471,268 @@ int pf_place_scores(int device, int n_bg, const float* const* bg_up, const float
     launch_place_sum(pb, s);
   }
   if (hipGetLastError() != hipSuccess) { g_create_error = "pf_place_scores: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+// pf_fields_transform, pf_place_search (field_xform.hip).  cos and sin of a rotation in degrees in fp64, exactly 0 or +-1 at the multiples of 90
+static void xform_trig(double rot_deg, double* c, double* s) {
+  const double a = remainder(rot_deg, 360.0);  // exact, in [-180, 180]
+  const double q = a / 90.0;
+  if (q == floor(q)) {
+    static const double C[5] = {-1.0, 0.0, 1.0, 0.0, -1.0}, S[5] = {0.0, -1.0, 0.0, 1.0, 0.0};
+    *c = C[(int)q + 2]; *s = S[(int)q + 2];
+    return;
+  }
+  const double rad = a * (M_PI / 180.0);
+  *c = cos(rad); *s = sin(rad);
+}
+// NULL and the size of the transformed field in out[2], or what is wrong
+static const char* xform_size(int h, int w, double scale, double rot, int32_t* out, std::string* why) {
+  if (h < 1 || w < 1 || (long long)h * w > INT32_MAX) { *why = fmt("a field of %d x %d, smaller than 1 x 1 or of 2^31 pixels or more", h, w); return why->c_str(); }
+  if (!(scale > 0.0) || !std::isfinite(scale)) { *why = fmt("scale %g, must be finite and > 0", scale); return why->c_str(); }
+  if (!std::isfinite(rot)) { *why = fmt("rotation %g, must be finite", rot); return why->c_str(); }
+  double c, s;
+  xform_trig(rot, &c, &s);
+  const double a = (double)h * fabs(c), b = (double)w * fabs(s), d = (double)w * fabs(c), e = (double)h * fabs(s);
+  const double ho = std::max(1.0, floor(scale * (a + b) + 0.5)), wo = std::max(1.0, floor(scale * (d + e) + 0.5));
+  if (!(ho * wo <= (double)INT32_MAX)) { *why = fmt("scale %g, rotation %g of a %d x %d field has 2^31 pixels or more", scale, rot, h, w); return why->c_str(); }
+  out[0] = (int32_t)ho; out[1] = (int32_t)wo;
+  return nullptr;
+}
+
+int pf_fields_transform_size(int h, int w, double scale, double rotation_deg, int32_t* out_hw) {
+  std::string why;
+  if (!out_hw) { g_create_error = "pf_fields_transform_size: h_out_hw is required"; return PF_ERR_ARG; }
+  if (const char* e = xform_size(h, w, scale, rotation_deg, out_hw, &why)) { g_create_error = std::string("pf_fields_transform_size: ") + e; return PF_ERR_ARG; }
+  return PF_OK;
+}
+
+// job k of a launch: the fp64 trig and 1 / s rounded to fp32 once
+static void xform_job(FieldXform* fx, int k, const float* up, const float* lat, const int32_t* hw, const double* var, const int32_t* out_hw, float* out_up,
+                      float* out_lat) {
+  double c, s;
+  xform_trig(var[1], &c, &s);
+  fx->h[k] = hw[0]; fx->w[k] = hw[1]; fx->ho[k] = out_hw[0]; fx->wo[k] = out_hw[1];
+  fx->c[k] = (float)c; fx->s[k] = (float)s; fx->inv[k] = (float)(1.0 / var[0]);
+  fx->up[k] = up; fx->lat[k] = lat; fx->out_up[k] = out_up; fx->out_lat[k] = out_lat;
+}
+
+int pf_fields_transform(int device, int n, const float* const* up, const float* const* lat, const int32_t* hw, const double* variants, const int32_t* out_hw,
+                        float* const* out_up, float* const* out_lat, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_fields_transform: " + m; return PF_ERR_ARG; };
+  if (n < 1 || !up || !lat || !hw || !variants || !out_hw || !out_up || !out_lat)
+    return bad("n >= 1, h_up, h_lat, h_hw, h_variants, h_out_hw, h_out_up and h_out_lat are required");
+  std::string why;
+  for (int k = 0; k < n; ++k) {
+    int32_t natural[2];
+    if (!up[k] || !lat[k] || !out_up[k] || !out_lat[k]) return bad(fmt("NULL field pointer of job %d", k));
+    if (const char* e = xform_size(hw[2 * k], hw[2 * k + 1], variants[2 * k], variants[2 * k + 1], natural, &why)) return bad(fmt("job %d: %s", k, e));
+    if (out_hw[2 * k] < 1 || out_hw[2 * k + 1] < 1 || (long long)out_hw[2 * k] * out_hw[2 * k + 1] > INT32_MAX)
+      return bad(fmt("job %d: output %d x %d, smaller than 1 x 1 or of 2^31 pixels or more", k, out_hw[2 * k], out_hw[2 * k + 1]));
+    if (misalign(up[k], 3) || misalign(lat[k], 3) || misalign(out_up[k], 3) || misalign(out_lat[k], 3)) return bad(fmt("job %d: fields must be aligned to 4 bytes", k));
+  }
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int k0 = 0; k0 < n; k0 += FieldXform::MAX) {
+    FieldXform fx;
+    fx.n = std::min(n - k0, (int)FieldXform::MAX);
+    for (int k = 0; k < fx.n; ++k) {
+      const int j = k0 + k;
+      xform_job(&fx, k, up[j], lat[j], hw + 2 * j, variants + 2 * j, out_hw + 2 * j, out_up[j], out_lat[j]);
+    }
+    launch_field_xform(fx, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_fields_transform: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+// pf_place_search: workspace = the transformed (up, lat) planes of every (object, variant), the packed planes (backgrounds, then (object, variant)), the
+// chunks' partial records of every (pair, variant) that fits, the valid pixels of every (object, variant), a BestHead per (pair, variant), the tiles'
+// partial bests; each region 256-byte aligned
+struct SearchPlan {
+  std::vector<int32_t> ohw;    // [n_obj][n_var][2]
+  size_t xf_bytes = 0, plane_bytes = 0, rec = 0, maps = 0, tiles = 0;
+};
+static bool search_fits(const int32_t* bg, const int32_t* o) { return o[0] <= bg[0] && o[1] <= bg[1]; }
+static size_t search_xf_bytes(const int32_t* hw) { return yaw_align((size_t)hw[0] * hw[1] * 3 * sizeof(float)); }
+static int search_tiles(long long np) { return (int)std::max(1LL, (np + BestBatch::TILE - 1) / BestBatch::TILE); }
+// NULL and the plan, or what is wrong with the arguments that set the layout
+static const char* search_plan(int n_bg, const int32_t* bg_hw, int n_obj, const int32_t* obj_hw, int n_pair, const int32_t* pairs, int n_var,
+                               const double* variants, int stride, SearchPlan* pl, std::string* why) {
+  if (n_bg < 1 || !bg_hw) return "n_bg >= 1 and h_bg_hw are required";
+  if (n_obj < 1 || !obj_hw) return "n_obj >= 1 and h_obj_hw are required";
+  if (n_pair < 1 || !pairs) return "n_pair >= 1 and h_pairs are required";
+  if (n_var < 1 || !variants) return "n_var >= 1 and h_variants are required";
+  if (stride < 1) { *why = fmt("stride %d, must be >= 1", stride); return why->c_str(); }
+  if ((long long)n_pair * n_var > INT32_MAX || (long long)n_obj * n_var > INT32_MAX) return "2^31 (pair, variant) or (object, variant) combinations or more";
+  for (int f = 0; f < n_bg; ++f)
+    if (bg_hw[2 * f] < 1 || bg_hw[2 * f + 1] < 1 || (long long)bg_hw[2 * f] * bg_hw[2 * f + 1] > INT32_MAX) {
+      *why = fmt("background %d is %d x %d, smaller than 1 x 1 or of 2^31 pixels or more", f, bg_hw[2 * f], bg_hw[2 * f + 1]);
+      return why->c_str();
+    }
+  pl->ohw.resize((size_t)n_obj * n_var * 2);
+  for (int o = 0; o < n_obj; ++o)
+    for (int v = 0; v < n_var; ++v) {
+      int32_t* t = &pl->ohw[((size_t)o * n_var + v) * 2];
+      std::string w2;
+      if (const char* e = xform_size(obj_hw[2 * o], obj_hw[2 * o + 1], variants[2 * v], variants[2 * v + 1], t, &w2)) {
+        *why = fmt("object %d, variant %d: %s", o, v, e);
+        return why->c_str();
+      }
+      pl->xf_bytes += search_xf_bytes(t);
+      pl->plane_bytes += place_plane_bytes(t);
+    }
+  for (int f = 0; f < n_bg; ++f) pl->plane_bytes += place_plane_bytes(bg_hw + 2 * f);
+  for (int k = 0; k < n_pair; ++k) {
+    const int b = pairs[2 * k], o = pairs[2 * k + 1];
+    if (b < 0 || b >= n_bg || o < 0 || o >= n_obj) {
+      *why = fmt("pair %d: index (%d, %d) of (%d backgrounds, %d objects)", k, b, o, n_bg, n_obj);
+      return why->c_str();
+    }
+    for (int v = 0; v < n_var; ++v) {
+      const int32_t* t = &pl->ohw[((size_t)o * n_var + v) * 2];
+      if (!search_fits(bg_hw + 2 * b, t)) { pl->tiles += 1; continue; }
+      const long long chunks = ((long long)t[0] * t[1] + PlaceBatch::CHUNK - 1) / PlaceBatch::CHUNK;
+      if (chunks > 65535) {
+        *why = fmt("pair %d, variant %d: the transformed object (%d x %d) has more than 65535 chunks of %d pixels", k, v, t[0], t[1], (int)PlaceBatch::CHUNK);
+        return why->c_str();
+      }
+      const long long np = (long long)((bg_hw[2 * b] - t[0]) / stride + 1) * ((bg_hw[2 * b + 1] - t[1]) / stride + 1);
+      pl->rec += (size_t)np * chunks;
+      pl->maps += (size_t)np * 3;
+      pl->tiles += search_tiles(np);
+    }
+  }
+  if (pl->tiles > (size_t)INT32_MAX) return "2^31 tiles of placements or more";
+  return nullptr;
+}
+static size_t search_ws_bytes(const SearchPlan& pl, int n_obj, int n_pair, int n_var) {
+  return 256 + pl.xf_bytes + pl.plane_bytes + yaw_align(pl.rec * 3 * sizeof(float)) + yaw_align((size_t)n_obj * n_var * sizeof(int)) +
+         yaw_align((size_t)n_pair * n_var * sizeof(BestHead)) + yaw_align(pl.tiles * sizeof(BestTile));
+}
+
+size_t pf_place_search_workspace_bytes(int n_bg, const int32_t* bg_hw, int n_obj, const int32_t* obj_hw, int n_pair, const int32_t* pairs, int n_var,
+                                       const double* variants, int stride) {
+  SearchPlan pl;
+  std::string why;
+  if (search_plan(n_bg, bg_hw, n_obj, obj_hw, n_pair, pairs, n_var, variants, stride, &pl, &why)) return 0;
+  return search_ws_bytes(pl, n_obj, n_pair, n_var);
+}
+
+int pf_place_search(int device, int n_bg, const float* const* bg_up, const float* const* bg_lat, const int32_t* bg_hw, int n_obj, const float* const* obj_up,
+                    const float* const* obj_lat, const int32_t* obj_hw, int n_pair, const int32_t* pairs, int n_var, const double* variants, int stride,
+                    double min_valid, double w_up, double w_lat, double* d_maps, size_t maps_doubles, double* d_best, double* d_var, void* ws, size_t ws_bytes,
+                    void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_place_search: " + m; return PF_ERR_ARG; };
+  SearchPlan pl;
+  std::string why;
+  if (const char* e = search_plan(n_bg, bg_hw, n_obj, obj_hw, n_pair, pairs, n_var, variants, stride, &pl, &why)) return bad(e);
+  if (!bg_up || !bg_lat || !obj_up || !obj_lat || !d_best || !d_var) return bad("h_bg_up, h_bg_lat, h_obj_up, h_obj_lat, d_best and d_var are required");
+  for (int f = 0; f < n_bg; ++f)
+    if (!bg_up[f] || !bg_lat[f]) return bad(fmt("NULL field pointer of background %d", f));
+  for (int f = 0; f < n_obj; ++f)
+    if (!obj_up[f] || !obj_lat[f]) return bad(fmt("NULL field pointer of object %d", f));
+  if (!(min_valid >= 0.0 && min_valid <= 1.0)) return bad(fmt("min_valid %g, must be in [0, 1]", min_valid));
+  if (!(w_up >= 0.0 && w_lat >= 0.0) || !std::isfinite(w_up) || !std::isfinite(w_lat)) return bad(fmt("weights (%g, %g), must be finite and >= 0", w_up, w_lat));
+  if (pl.maps > 0 && (!d_maps || maps_doubles < pl.maps)) return bad(fmt("d_maps needs %zu doubles, got %zu", pl.maps, d_maps ? maps_doubles : (size_t)0));
+  if (misalign(d_maps, 7) || misalign(d_best, 7) || misalign(d_var, 7)) return bad("d_maps, d_best and d_var must be aligned to 8 bytes");
+  const size_t need = search_ws_bytes(pl, n_obj, n_pair, n_var);
+  if (!ws || ws_bytes < need) return bad(fmt("needs %zu workspace bytes, got %zu", need, ws_bytes));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // 1. every (object, variant), object-major
+  const int n_ov = n_obj * n_var;
+  std::vector<float*> xf(n_ov);
+  for (int k0 = 0; k0 < n_ov; k0 += FieldXform::MAX) {
+    FieldXform fx;
+    fx.n = std::min(n_ov - k0, (int)FieldXform::MAX);
+    for (int k = 0; k < fx.n; ++k) {
+      const int j = k0 + k, o = j / n_var, v = j - o * n_var;
+      const int32_t* t = &pl.ohw[(size_t)j * 2];
+      xf[j] = reinterpret_cast<float*>(p);
+      xform_job(&fx, k, obj_up[o], obj_lat[o], obj_hw + 2 * o, variants + 2 * v, t, xf[j], xf[j] + (size_t)t[0] * t[1] * 2);
+      p += search_xf_bytes(t);
+    }
+    launch_field_xform(fx, s);
+  }
+  // 2. the packed planes: backgrounds, then (object, variant)
+  const int n_field = n_bg + n_ov;
+  std::vector<float2*> plane(n_field);
+  for (int f0 = 0; f0 < n_field; f0 += PlacePack::MAX) {
+    PlacePack pp;
+    pp.n = std::min(n_field - f0, (int)PlacePack::MAX);
+    for (int k = 0; k < pp.n; ++k) {
+      const int f = f0 + k;
+      const int32_t* hw = f < n_bg ? bg_hw + 2 * f : &pl.ohw[(size_t)(f - n_bg) * 2];
+      pp.npx[k] = hw[0] * hw[1];
+      pp.up[k] = f < n_bg ? bg_up[f] : xf[f - n_bg];
+      pp.lat[k] = f < n_bg ? bg_lat[f] : xf[f - n_bg] + (size_t)hw[0] * hw[1] * 2;
+      pp.out[k] = plane[f] = reinterpret_cast<float2*>(p);
+      p += place_plane_bytes(hw);
+    }
+    launch_place_pack(pp, s);
+  }
+  float* part = reinterpret_cast<float*>(p);
+  p += yaw_align(pl.rec * 3 * sizeof(float));
+  int* cnt = reinterpret_cast<int*>(p);
+  p += yaw_align((size_t)n_ov * sizeof(int));
+  BestHead* head = reinterpret_cast<BestHead*>(p);
+  p += yaw_align((size_t)n_pair * n_var * sizeof(BestHead));
+  BestTile* tile = reinterpret_cast<BestTile*>(p);
+  for (int k0 = 0; k0 < n_ov; k0 += BestCount::MAX) {
+    BestCount bc;
+    bc.n = std::min(n_ov - k0, (int)BestCount::MAX);
+    for (int k = 0; k < bc.n; ++k) {
+      const int32_t* t = &pl.ohw[(size_t)(k0 + k) * 2];
+      bc.npx[k] = t[0] * t[1];
+      bc.plane[k] = plane[n_bg + k0 + k];
+      bc.cnt[k] = cnt + k0 + k;
+    }
+    launch_place_count(bc, s);
+  }
+  // 3. the scores of every (pair, variant) that fits, pf_place_scores' launches; then every (pair, variant)'s partial bests
+  const long long n_pv = (long long)n_pair * n_var;
+  size_t part0 = 0, out0 = 0;
+  int tile0 = 0;
+  for (long long i0 = 0; i0 < n_pv; i0 += PlaceBatch::MAX) {
+    PlaceBatch pb;
+    BestBatch bb;
+    pb.n = 0; pb.stride = stride; pb.max_tiles = 0; pb.max_chunks = 0; pb.part = part; pb.out = d_maps;
+    bb.n = (int)std::min(n_pv - i0, (long long)BestBatch::MAX);
+    bb.max_tiles = 1; bb.min_valid = min_valid; bb.w_up = w_up; bb.w_lat = w_lat; bb.head = head; bb.tile = tile;
+    for (int k = 0; k < bb.n; ++k) {
+      const int pair = (int)((i0 + k) / n_var), v = (int)((i0 + k) - (long long)pair * n_var);
+      const int b = pairs[2 * pair], o = pairs[2 * pair + 1], ov = o * n_var + v;
+      const int32_t *B = bg_hw + 2 * b, *t = &pl.ohw[(size_t)ov * 2];
+      BestEntry& e = bb.e[k];
+      e = BestEntry{nullptr, cnt + ov, 0, 1, t[0], t[1], tile0, (int)(i0 + k)};
+      if (search_fits(B, t)) {
+        const int P = (B[0] - t[0]) / stride + 1, Q = (B[1] - t[1]) / stride + 1, np = P * Q;  // <= the background's pixels < 2^31
+        const int chunks = (int)(((long long)t[0] * t[1] + PlaceBatch::CHUNK - 1) / PlaceBatch::CHUNK);
+        pb.pr[pb.n++] = PlacePair{plane[b], plane[n_bg + ov], B[1], t[1], t[0] * t[1], Q, np, chunks, part0, out0};
+        pb.max_tiles = std::max(pb.max_tiles, (int)(((long long)np + PlaceBatch::TILE - 1) / PlaceBatch::TILE));
+        pb.max_chunks = std::max(pb.max_chunks, chunks);
+        e.map = d_maps + out0 * 3; e.np = np; e.Q = Q;
+        part0 += (size_t)np * chunks;
+        out0 += (size_t)np;
+      }
+      const int tiles = search_tiles(e.np);
+      bb.max_tiles = std::max(bb.max_tiles, tiles);
+      tile0 += tiles;
+    }
+    if (pb.n > 0) {
+      launch_place_score(pb, s);
+      launch_place_sum(pb, s);
+    }
+    launch_place_best_tiles(bb, s);
+  }
+  launch_place_best_pairs(n_pair, n_var, stride, head, tile, d_best, d_var, s);
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_place_search: kernel launch failed"; return PF_ERR_DEVICE; }
   return PF_OK;
 }
 

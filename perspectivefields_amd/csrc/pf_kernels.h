@@ -634,6 +634,56 @@ void launch_place_score(const PlaceBatch& pb, hipStream_t s);  // the store pass
 void launch_place_sum(const PlaceBatch& pb, hipStream_t s);    // the chunks of each placement added in chunk order in fp64
 static_assert(sizeof(PlacePair) == 56 && sizeof(PlaceBatch) <= 4096 && sizeof(PlacePack) <= 4096, "PlaceBatch and PlacePack fit the kernel arguments");
 
+// similarity transforms of perspective fields and the best placement over variants (field_xform.hip, include/pf_hip.h pf_fields_transform and
+// pf_place_search): up to FieldXform::MAX (source, variant) jobs per launch, then up to BestBatch::MAX (pair, variant) score maps per launch
+struct FieldXform {
+  static constexpr int MAX = 32;
+  int n;                         // jobs of this launch
+  int h[MAX], w[MAX];            // source size
+  int ho[MAX], wo[MAX];          // output size h', w'
+  float c[MAX], s[MAX], inv[MAX];  // cos phi, sin phi, 1 / scale: fp64 on the host, rounded once
+  const float* up[MAX];          // (2, h, w) degrees
+  const float* lat[MAX];         // (h, w) degrees
+  float* out_up[MAX];            // (2, h', w')
+  float* out_lat[MAX];           // (h', w')
+};
+void launch_field_xform(const FieldXform& fx, hipStream_t s);
+struct BestCount {
+  static constexpr int MAX = 32;
+  int n;                     // packed planes of this launch
+  int npx[MAX];
+  const float2* plane[MAX];  // place_pack_kernel's records
+  int* cnt[MAX];             // the plane's valid pixels
+};
+void launch_place_count(const BestCount& bc, hipStream_t s);
+struct BestHead {        // one per (pair, variant), written by the tile pass for the pair pass
+  const double* map;     // the (pair, variant)'s [np][3] records, NULL for a skipped variant
+  int tile0, tiles;      // its partial bests in `tile`
+  int Q, cnt, ho, wo;    // placements across; valid pixels and size of the transformed object
+};
+struct BestTile { double pfd; long long at; };  // the lowest pfd of a tile and its row-major placement, the first of equal ones; at = -1 with +inf
+struct BestEntry {
+  const double* map;     // NULL: skipped
+  const int* cnt;
+  int np, Q, ho, wo;
+  int tile0;             // the entry's first partial in `tile`
+  int head;              // pair * n_var + variant
+};
+struct BestBatch {
+  static constexpr int MAX = 32;
+  static constexpr int TILE = 256;  // placements per block of the tile pass
+  int n, max_tiles;                 // entries of this launch; largest max(1, ceil(np / TILE))
+  double min_valid, w_up, w_lat;
+  BestHead* head;
+  BestTile* tile;
+  BestEntry e[MAX];
+};
+void launch_place_best_tiles(const BestBatch& bb, hipStream_t s);
+// one block per pair: d_var[pair][variant][6] and d_best[pair][7] from the heads and partials of every variant
+void launch_place_best_pairs(int n_pair, int n_var, int stride, const BestHead* head, const BestTile* tile, double* d_best, double* d_var,
+                             hipStream_t s);
+static_assert(sizeof(FieldXform) <= 4096 && sizeof(BestCount) <= 4096 && sizeof(BestBatch) <= 4096, "FieldXform, BestCount and BestBatch fit the kernel arguments");
+
 // perspective fields drawn over their images (draw_fields.hip, include/pf_hip.h pf_draw_fields): up to DrawBatch::MAX images per launch, per-image sizes
 // and pointers in the kernel arguments
 struct DrawBatch {

@@ -80,6 +80,11 @@ _SIGNATURES = {
     "pf_yaw_moments": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
     "pf_place_scores_workspace_bytes": (_c.c_size_t, [_c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int]),
     "pf_place_scores": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _P, _P, _P, _c.c_int, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
+    "pf_fields_transform_size": (_c.c_int, [_c.c_int, _c.c_int, _c.c_double, _c.c_double, _P]),
+    "pf_fields_transform": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "pf_place_search_workspace_bytes": (_c.c_size_t, [_c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int]),
+    "pf_place_search": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _P, _P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_double, _c.c_double, _c.c_double,
+                                   _P, _c.c_size_t, _P, _P, _P, _c.c_size_t, _P]),
     "pf_draw_fields_workspace_bytes": (_c.c_size_t, [_c.c_int, _P, _c.c_int]),
     "pf_draw_fields": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_float, _P, _c.c_int, _P, _c.c_size_t, _P]),
     "pf_field_errors_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
