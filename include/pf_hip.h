@@ -263,7 +263,8 @@ int pf_debug_ranges(pf_handle h, int max_records, char* names /*[max][96]*/, lon
 #define PF_DISPATCH_REAL_PEAK_BYTES 15        /* what the forward allocated from the workspace (main region + ParamNet region) */
 #define PF_DISPATCH_DRY_PEAK_BYTES 16         /* what pf_workspace_bytes' dry run sized for them; real > dry in either region: the call returns PF_ERR_WORKSPACE */
 #define PF_DISPATCH_CNX_RB_LAUNCHES 17        /* row-block fused ConvNeXt block MLPs of the 384- / 768-channel stages (cnx_rb.hip); not part of RB_LAUNCHES */
-#define PF_DISPATCH_COLS 18
+#define PF_DISPATCH_DEC_EARLY_TAKEN 18        /* 1: the decoders' first convs of levels 0-2 (PF_DEC_EARLY=2: and r1c1) were issued on a side stream beside MiT stage 4 */
+#define PF_DISPATCH_COLS 19
 int pf_last_dispatch(pf_handle h, int64_t* out, int n);
 
 /* The same for a whole batch in one launch per 32 images (the reference's per-image Python loop,

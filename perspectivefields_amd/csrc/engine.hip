@@ -262,12 +262,19 @@ struct pf_engine {
   unsigned short* ll_s7_w = nullptr; float* ll_s7_tab = nullptr; unsigned short* pe_s7_w = nullptr; float* pe_s7_tab = nullptr;
   int attn64 = 1;            // PF_ATTN64: the attention half of the one-head stage-1 blocks (q, attention, proj, residual) as one kernel (attn_block.hip)
   int s3_split = 1;          // PF_S3_SPLIT: MiT stage 3 on two half-batches / two streams (mit(), "the stage-3 split")
+  int dec_early = 2;         // PF_DEC_EARLY: the decoders' launches that need nothing of MiT stage 4 are issued on a side stream right after the stage-3 norm, beside stage 4 and
+                             // decoder levels 3 / 2 (dec_early_issue(), "the early decoder start"): 1 the folded first convs fold[0..2], 2 also r1c1[0..2]; 0 = forward order
+  int dec_early_stream = 2;  // PF_DEC_EARLY_STREAM: 2 = on `side2` (stage 4 keeps its q-beside-kv fork on `side`), 1 = on `side` (stage 4 runs unforked while the window is open)
+  int dec_early_min_batch = 4;  // PF_DEC_EARLY_MIN_BATCH: as for the q fork -- below it every launch is a fraction of a round and a second stream only adds event traffic
+  int dec_early_joined_max = 8;  // PF_DEC_EARLY_JOINED_MAX: largest batch that takes the path in a JOINED forward (pf_set_defer_params off, graph capture)
+  bool dry_early = false;    // workspace_bytes: which of the two layouts (hoisted decoder tensors or not) the dry run walks
   int side_stream_mode = 1;  // 1 (default): the q projection of a MiT block runs on a second stream next to the sr conv + kv GEMM (both consume LayerNorm-1's
                              // output, attention joins them) -- small launches that each fill a fraction of the chip: +0.6 % (3 x A/B on one box, profiles/
                              // r02_negative_results.md); 2: also the low-level encoder conv next to MiT stage 3 (+0.1 %, noise); PF_SIDE_STREAM=0: one stream.
                              // Never forked while tuning or profiling (per-launch events time one stream)
   hipStream_t side = nullptr, side2 = nullptr;   // side: the q projections; side2: the low-level encoder conv, launched next to MiT stage 3
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_ll = nullptr;
+  hipEvent_t ev_de_fork = nullptr, ev_de[3] = {nullptr, nullptr, nullptr};   // the early decoder start: c3 is written / level k's hoisted launches are done
   // Deferred ParamNet (pf_set_defer_params): the ConvNeXt branch of forward i runs on an internal stream behind the decoders of forward i and is NOT joined at the
   // end of the call -- forward i + 1's backbone (other images: no dependency) runs next to it.  Both are chains of small, latency-bound launches that leave most of
   // the chip idle (MiT stage 3: 13 % MFMA-busy; ConvNeXt stages 3-4 likewise), and their kernels co-reside (small LDS, 4 waves).  d_params of forward i is valid in
@@ -307,13 +314,16 @@ struct pf_engine {
   // overlap -- the engine therefore creates only the streams its mode needs (side2 only for PF_SIDE_STREAM=2); with the null stream, `side` and the ParamNet stream
   // a forward uses three queues (profiles/r04_defer_params.md: with nine streams in one process the deferred branch lost its whole gain).
   bool side_ready() {
-    if (side && (side2 || side_stream_mode < 2)) return true;
+    const bool need2 = side_stream_mode >= 2 || (dec_early > 0 && dec_early_stream != 1);  // caller's stream, side, side2, pstream: the four hardware queues of a process
+    if (side && (side2 || !need2)) return true;
     if (!side) {
       if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) { side = nullptr; return false; }
       if (hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) != hipSuccess ||
           hipEventCreateWithFlags(&ev_ll, hipEventDisableTiming) != hipSuccess) return false;
+      for (hipEvent_t* e : {&ev_de_fork, &ev_de[0], &ev_de[1], &ev_de[2]})
+        if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) { *e = nullptr; return false; }
     }
-    if (side_stream_mode >= 2 && !side2 && hipStreamCreateWithFlags(&side2, hipStreamNonBlocking) != hipSuccess) { side2 = nullptr; return false; }
+    if (need2 && !side2 && hipStreamCreateWithFlags(&side2, hipStreamNonBlocking) != hipSuccess) { side2 = nullptr; return false; }
     return true;
   }
   // A FORK WINDOW runs from a `Ctx c2 = c` -- a COPY of the bump allocator that issues launches on a side stream -- to the join of that stream.  Both contexts
@@ -321,6 +331,9 @@ struct pf_engine {
   // runs on the side stream).  Both allocating would hand two streams the same scratch: counted, timing-free, in PF_DISPATCH_FORK_ALLOC_CONFLICTS -- 0 after every forward.
   struct ForkWin { bool open = false, side_alloced = false; size_t nalloc0 = 0; };
   ForkWin fw_q, fw_ll;   // q beside kv / the stage-3 split (never nested in each other); the low-level encoder beside stages 3 / 4
+  ForkWin fw_de;         // the early decoder start: open from the stage-3 norm to decoder level 0 (stage 4's q windows open and close inside it)
+  // The early decoder start's state of one forward: the hoisted tensors of levels 0-2 (p: fold[k]'s outputs; t: r1c1[k]'s, mode 2), allocated in front of stage 4
+  struct DecEarly { bool layout = false, issued = false; Ten p[3][2], t[3][2]; } de;
   Ctx fork_open(Ctx& c, hipStream_t s, ForkWin& w) {
     Ctx c2 = c;
     c2.s = s;
@@ -1294,7 +1307,7 @@ struct pf_engine {
         for (MitBlock& mb : st.blocks) {
           if (blk >= 0) tap(c, fmt("mit.s%d.b%d", s + 1, blk), x, B, Ho, Wo, C);  // the previous block's output (token stream, pre stage norm)
           ++blk;
-          one_block(c, mb, blk, B, M, Mkv, x, xalt, xn, qb, ab, srb, srn, kvb, hb, h2, B, true);
+          one_block(c, mb, blk, B, M, Mkv, x, xalt, xn, qb, ab, srb, srn, kvb, hb, h2, B, !(de.issued && dec_early_stream == 1));  // (`side` is taken while the early decoder window runs on it)
         }
       }
       c.release(mk);
@@ -1304,6 +1317,7 @@ struct pf_engine {
       feats[s] = Ten(x, xs);
       cur = feats[s];
       H = Ho; W = Wo;
+      if (s == 2) dec_early_issue(c, B, feats);  // c1 ... c3 are written: what the decoders can do without c4 starts here, beside stage 4
     }
   }
 
@@ -1316,17 +1330,85 @@ struct pf_engine {
   // With `sba` a conv's epilogue writes split planes for the next conv (and fp32 only where a residual add reads it).
   // pred_fused(): the regression heads' 1x1 prediction convs run inside conv_fuse_conv1's epilogue (no 32-channel map in HBM)
   bool pred_fused() const { return fuse_pred && arch != PF_ARCH_PERSNET_CLS && nterms == NT_F16X3 && split_bf16; }
+  // a pair of per-head tensors, contiguous as [2][...] in fp32 and in every split plane
+  static void dec_pair(Ctx& c, size_t per_head, bool want_f32, bool want_sb, Ten& a, Ten& b) {
+    a = Ten(); b = Ten();
+    if (want_f32) { a.f = c.alloc(2 * per_head); b.f = a.f + per_head; }
+    if (want_sb) { a.s = c.alloc_sb(2 * per_head); b.s = a.s; b.s.p = a.s.p + per_head; }
+  }
+  bool dec_sr() const { return (sba && nterms != NT_F16X3) || (sba_heads && !sba && nterms == NT_F16X3 && split_bf16); }  // heads_fwd's SR
+  // The two decoder launches of a level that do not depend on the deeper level (heads_fwd): relu(fold[k](c_k)) and relu(r1c1[k](.)), both heads grouped
+  void dec_fold(Ctx& c, int k, int B, Ten feats[4], const Ten& p0, const Ten& p1) {
+    const int h = NET >> (k + 2);
+    ConvCall cc[2] = {{&heads[0].fold[k], feats[k], p0}, {&heads[1].fold[k], feats[k], p1}};
+    conv_g(c, 2, cc, B, h, h, ACT_NONE, 1);                                   // relu(_ck), Linear folded into the conv
+  }
+  void dec_r1c1(Ctx& c, int k, int B, const Ten& p0, const Ten& p1, const Ten& t0, const Ten& t1) {
+    const int h = NET >> (k + 2);
+    ConvCall a[2] = {{&heads[0].r1c1[k], p0, t0}, {&heads[1].r1c1[k], p1, t1}};
+    conv_g(c, 2, a, B, h, h, ACT_RELU);
+  }
+  // THE EARLY DECODER START (PF_DEC_EARLY).  heads_fwd walks the levels k = 3 ... 0 in order, but at levels 0-2 the folded first conv fold[k] reads only c_{k+1} =
+  // feats[k], and r1c1[k] reads only fold[k]'s output: the deeper level enters at r1c2[k], as the up[k+1] residual.  c1 ... c3 are complete when the stage-3 norm
+  // has run, so these launches -- large ones that fill the chip -- are issued there on a side stream, behind an event on the caller's stream, beside MiT stage 4
+  // (~25 dependent launches of 50 x N/64 small blocks) and the 10^2 / 20^2 decoder levels (one round of blocks each), which leave most CUs empty.  Same kernels, same
+  // tiles, same inputs: bit-identical to the forward order (tests/test_gpu_dec_early.py).
+  //   * order on the side stream: level 2, 1, 0 -- the order in which heads_fwd needs them; one event per level, which heads_fwd waits for in front of the
+  //     first consumer of the level's hoisted tensor (r1c1[k] in mode 1, r1c2[k] in mode 2).  The wait at level 0 is the join: every forward takes it.
+  //   * workspace: the hoisted outputs are allocated HERE, below stage 4's buffers, and are never released: no mark / release pair of stage 4 or of a decoder level
+  //     covers them.  The scratch of the early launches (split-K partials) lies right above them and the parent allocator SKIPS that range for the rest of the
+  //     forward, so the window's copy and the parent never allocate from one offset although both allocate.  The dry run walks the same code (dry_early), and
+  //     workspace_bytes sizes both layouts, this one and the forward order's, because the gates below can send a forward of either kind through one engine.
+  //   * the deferred ParamNet branch of the previous forward may still run: it reads its input map `pn` and works in its own region behind the main one; nothing
+  //     here touches either (run(): the join stays in front of the decoder levels; the first writer of `pn` is conv_fuse_conv1's epilogue).
+  //   * gates: the plain forward only -- not the debug forward (taps and range records keep forward order), not while tuning, not inside a full per-launch profile
+  //     (one stream; pf_profile_phases' decoder phase must hold the decoders' launches), not with PF_SIDE_STREAM=0, not below dec_early_min_batch.  Under graph
+  //     capture the fork and the join are event edges like the q fork's and are captured as such (the window closes inside every forward).
+  void dec_early_issue(Ctx& c, int B, Ten feats[4]) {
+    const bool plain = !c.dbg && !c.tuning && (!c.prof || c.prof->min_work > 0.0);
+    const bool want = dec_early > 0 && fold_mlp && side_stream_mode && B >= dec_early_min_batch && plain;
+    // joined forwards (no deferred ParamNet branch) gain at B = 8 (+2.4 %) but LOSE at B = 32 (-2.6 %, profiles/r08_dec_early.md): there the path is taken only up to
+    // dec_early_joined_max images; with the deferred branch it gains at every measured batch (8 ... 64)
+    const bool pays = defer_params || B <= dec_early_joined_max;
+    if (!want || !(c.dry ? dry_early : (pays && can_fork(c) && ev_de_fork && ev_de[0] && ev_de[1] && ev_de[2]))) return;
+    const bool SR = dec_sr();
+    de.layout = true;
+    for (int k = 2; k >= 0; --k) {
+      const size_t M = (size_t)B * (NET >> (k + 2)) * (NET >> (k + 2));
+      dec_pair(c, M * DEC_FEAT, true, SR, de.p[k][0], de.p[k][1]);
+      if (dec_early >= 2) dec_pair(c, M * DEC_FEAT, !SR, SR, de.t[k][0], de.t[k][1]);
+    }
+    hipStream_t es = dec_early_stream == 1 ? side : side2;
+    Ctx c2 = c;
+    if (!c.dry) {
+      (void)hipEventRecord(ev_de_fork, c.s);
+      (void)hipStreamWaitEvent(es, ev_de_fork, 0);
+      c2 = fork_open(c, es, fw_de);
+      c.count(PF_DISPATCH_DEC_EARLY_TAKEN);
+      de.issued = true;
+    }
+    c2.peak = c2.off;  // from here: the high-water mark of the early launches' scratch
+    for (int k = 2; k >= 0; --k) {
+      dec_fold(c2, k, B, feats, de.p[k][0], de.p[k][1]);
+      if (dec_early >= 2) dec_r1c1(c2, k, B, de.p[k][0], de.p[k][1], de.t[k][0], de.t[k][1]);
+      if (!c.dry) (void)hipEventRecord(ev_de[k], es);
+    }
+    c.off = c2.peak;   // the parent skips that scratch: reserved until the forward ends
+    if (c.off > c.peak) c.peak = c.off;
+    if (c2.max_conv_out > c.max_conv_out) c.max_conv_out = c2.max_conv_out;
+  }
+  // heads_fwd, in front of the first consumer of level k's hoisted tensor
+  void dec_early_wait(Ctx& c, int k) {
+    if (!de.issued) return;
+    (void)hipStreamWaitEvent(c.s, ev_de[k], 0);
+    if (k == 0) { fork_join(c, fw_de); de.issued = false; }
+  }
   void heads_fwd(Ctx& c, int B, Ten feats[4], Ten llf, float* t32 /*[2][B][320][320][32], unused when the heads are fused*/, float* pg, float* pl, float* pn) {
     const bool S = sba && nterms != NT_F16X3;  // the 3x3 halo kernels of the decoder stage fp32 inputs: split-f16 planes only in MiT / ConvNeXt
     const bool SR = S || (sba_heads && !sba && nterms == NT_F16X3 && split_bf16);  // ResidualConvUnit chain in split planes (PF_SBA_HEADS: fp16 planes, halo kernel ASB)
     Head& hg = heads[0];
     Head& hl = heads[1];
-    // a pair of per-head tensors, contiguous as [2][...] in fp32 and in every split plane
-    auto pair = [&](size_t per_head, bool want_f32, bool want_sb, Ten& a, Ten& b) {
-      a = Ten(); b = Ten();
-      if (want_f32) { a.f = c.alloc(2 * per_head); b.f = a.f + per_head; }
-      if (want_sb) { a.s = c.alloc_sb(2 * per_head); b.s = a.s; b.s.p = a.s.p + per_head; }
-    };
+    auto pair = [&](size_t per_head, bool want_f32, bool want_sb, Ten& a, Ten& b) { dec_pair(c, per_head, want_f32, want_sb, a, b); };
     // The two largest bilinear x2 maps -- up[0] (160^2 x 256) feeding conv_fuse_conv0 and the 320^2 x 64 map feeding
     // conv_fuse_conv1 (decode_head.py:284-286, gravity_head.py:170-172) -- are never materialised: the consuming 3x3 convs
     // interpolate them while staging their input halo tiles (ConvParams::ups; same expression, bit-identical results).
@@ -1342,11 +1424,15 @@ struct pf_engine {
       const int h = NET >> (k + 2);
       const size_t M = (size_t)B * h * h;
       const size_t mk = c.mark();
+      // levels 0-2 of a forward with the early decoder start (dec_early_issue): fold[k] -- and r1c1[k] in mode 2 -- are already issued on the side stream, into
+      // tensors allocated in front of MiT stage 4; this stream waits for the level's event in front of the first launch that reads one of them
+      const bool hoist = de.layout && k < 3, hoist_t = hoist && dec_early >= 2;
       Ten p0, p1;
-      pair(M * DEC_FEAT, true, SR, p0, p1);
-      if (fold_mlp) {
-        ConvCall cc[2] = {{&hg.fold[k], feats[k], p0}, {&hl.fold[k], feats[k], p1}};
-        conv_g(c, 2, cc, B, h, h, ACT_NONE, 1);                               // relu(_ck), Linear folded into the conv
+      if (hoist) { p0 = de.p[k][0]; p1 = de.p[k][1]; }
+      else pair(M * DEC_FEAT, true, SR, p0, p1);
+      if (hoist) {
+      } else if (fold_mlp) {
+        dec_fold(c, k, B, feats, p0, p1);
       } else {
         Ten e0, e1;
         pair(M * DEC_EMBED, !S, S, e0, e1);
@@ -1358,9 +1444,10 @@ struct pf_engine {
       Ten o0 = p0, o1 = p1;
       if (k < 3) {                                                            // o = relu(up(prev) + RCU1(_ck))
         Ten t0, t1;
-        pair(M * DEC_FEAT, !SR, SR, t0, t1);
-        ConvCall a[2] = {{&hg.r1c1[k], p0, t0}, {&hl.r1c1[k], p1, t1}};
-        conv_g(c, 2, a, B, h, h, ACT_RELU);
+        if (hoist_t) { t0 = de.t[k][0]; t1 = de.t[k][1]; }
+        else pair(M * DEC_FEAT, !SR, SR, t0, t1);
+        if (hoist && !c.dry) dec_early_wait(c, k);                            // r1c1 reads p (mode 1); r1c2 reads t and p (mode 2)
+        if (!hoist_t) dec_r1c1(c, k, B, p0, p1, t0, t1);
         pair(M * DEC_FEAT, true, SR, o0, o1);
         ConvCall b2[2] = {{&hg.r1c2[k], t0, o0, p0.f, up[k + 1][0].f}, {&hl.r1c2[k], t1, o1, p1.f, up[k + 1][1].f}};
         conv_g(c, 2, b2, B, h, h, ACT_NONE, 1);
@@ -1503,6 +1590,7 @@ struct pf_engine {
     const bool Sh = sba && nterms != NT_F16X3;  // as in heads_fwd: the decoder's halo kernels read fp32
     const Ten llf = c.ten((size_t)B * (NET / 2) * (NET / 2) * LL_CH, !Sh, Sh);
     ll_forked = false;
+    de = DecEarly();
     mit(c, B, x0, feats, &llf);
     if (!c.dry && c.prof) c.prof->mark(PH_LL, c.s);
     if (ll_forked) { (void)hipStreamWaitEvent(c.s, ev_ll, 0); fork_join(c, fw_ll); }
@@ -1518,6 +1606,9 @@ struct pf_engine {
     cp.off = 0; cp.peak = 0;
     if (!c.dry) cp.base = c.base + pn_off[B];
     float* pn = has_param ? cp.alloc((size_t)B * NET * NET * 4) : nullptr;
+    // The join of the previous forward's deferred branch stays in front of the decoder levels.  The first launch of this forward that writes `pn` is the last one,
+    // conv_fuse_conv1 (its fused prediction epilogue; launch_pred_regression when the heads are not fused), so the decoder launches that dec_early_issue() has
+    // already put on a side stream -- fold[k] / r1c1[k], which read c1 ... c3 and write the main region only -- are on the safe side of it.
     if (!c.dry && pn_pending) {  // the previous forward's deferred branch still reads pn / writes its activations: the decoders below overwrite pn
       issue_deferred();
       (void)hipStreamWaitEvent(c.s, ev_pn_done, 0);
@@ -1566,15 +1657,25 @@ struct pf_engine {
   size_t workspace_bytes(int B, bool with_scratch = false) {
     auto it = ws_cache.find(B);
     if (it == ws_cache.end()) {
-      Ctx c{nullptr, 4096, 0, 0, true, nullptr};
-      c.sb_planes = nterms == NT_F16X3 ? 2 : 3;
-      run(c, B, nullptr, true, nullptr, nullptr, nullptr);
-      const size_t main_peak = (c.peak + 255) & ~(size_t)255, total = main_peak + ((run_pn_peak + 255) & ~(size_t)255);
+      // two layouts, one engine: the forward order's and the early decoder start's (dec_early_issue: hoisted decoder tensors below stage 4) -- which one a forward
+      // takes is decided per call (debug forward, profile window, ...), so the regions are sized for the larger of the two
+      size_t main_peak = 0, pn_bytes = 0, conv_out = 0;
+      for (int early = 0; early < 2; ++early) {
+        Ctx c{nullptr, 4096, 0, 0, true, nullptr};
+        c.sb_planes = nterms == NT_F16X3 ? 2 : 3;
+        dry_early = early != 0;
+        run(c, B, nullptr, true, nullptr, nullptr, nullptr);
+        dry_early = false;
+        main_peak = std::max(main_peak, (c.peak + 255) & ~(size_t)255);
+        pn_bytes = std::max(pn_bytes, (run_pn_peak + 255) & ~(size_t)255);
+        conv_out = std::max(conv_out, c.max_conv_out);
+      }
+      const size_t total = main_peak + pn_bytes;
       pn_off[B] = main_peak;
-      pn_peak[B] = (run_pn_peak + 255) & ~(size_t)255;
+      pn_peak[B] = pn_bytes;
       ws_cache[B] = total + 4096;
       scratch_off[B] = total;
-      scratch_elems[B] = c.max_conv_out;
+      scratch_elems[B] = conv_out;
       it = ws_cache.find(B);
     }
     return it->second + ((with_scratch || autotune) ? scratch_elems[B] * 10 + 4096 : 0);
@@ -1605,7 +1706,7 @@ struct pf_engine {
     if (!tune) c.rep = dispatch;
     const LaunchCounts lc0 = g_launch_counts;
     g_launch_counts.splitk_max = 0;
-    fw_q.open = fw_ll.open = false;
+    fw_q.open = fw_ll.open = fw_de.open = false;
     run(c, B, in, is_u8, pg, pl, params);
     const LaunchCounts lc1 = g_launch_counts;
     g_launch_counts.splitk_max = std::max(lc0.splitk_max, lc1.splitk_max);
@@ -1686,6 +1787,10 @@ int pf_create(pf_handle* out, int device, int arch) {
 #endif
   if (const char* v = getenv("PF_SIDE_STREAM")) e->side_stream_mode = atoi(v);
   if (const char* v = getenv("PF_S3_SPLIT")) e->s3_split = atoi(v);
+  if (const char* v = getenv("PF_DEC_EARLY")) e->dec_early = atoi(v);
+  if (const char* v = getenv("PF_DEC_EARLY_STREAM")) e->dec_early_stream = atoi(v) == 1 ? 1 : 2;
+  if (const char* v = getenv("PF_DEC_EARLY_MIN_BATCH")) e->dec_early_min_batch = atoi(v);
+  if (const char* v = getenv("PF_DEC_EARLY_JOINED_MAX")) e->dec_early_joined_max = atoi(v);
   if (const char* v = getenv("PF_ATTN64")) e->attn64 = atoi(v);
   if (const char* v = getenv("PF_STEM7")) e->stem7 = atoi(v);
   if (const char* v = getenv("PF_THIN128")) e->thin128 = atoi(v);
@@ -1752,6 +1857,7 @@ int pf_destroy(pf_handle h) {
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
   if (h->ev_ll) (void)hipEventDestroy(h->ev_ll);
+  for (hipEvent_t e : {h->ev_de_fork, h->ev_de[0], h->ev_de[1], h->ev_de[2]}) if (e) (void)hipEventDestroy(e);
   if (h->side) (void)hipStreamDestroy(h->side);
   if (h->side2) (void)hipStreamDestroy(h->side2);
   if (h->pstream) { (void)hipStreamSynchronize(h->pstream); (void)hipStreamDestroy(h->pstream); }

@@ -23,7 +23,7 @@ PF_OK = 0
 # columns of pf_last_dispatch (include/pf_hip.h PF_DISPATCH_*), in order
 DISPATCH_COLUMNS = ("batch", "s3_split_taken", "rb_launches", "splitk_launches", "splitk_max_factor", "wino_launches", "wino_half_launches", "thin128_launches",
                     "attn64_launches", "mit_mlp_fused_launches", "ln_kernel_launches", "conv_launches", "sb_tensors", "forks", "fork_alloc_conflicts",
-                    "real_peak_bytes", "dry_peak_bytes", "cnx_rb_launches")
+                    "real_peak_bytes", "dry_peak_bytes", "cnx_rb_launches", "dec_early_taken")
 _STATUS = {0: "PF_OK", -1: "PF_ERR_ARG", -2: "PF_ERR_DEVICE", -3: "PF_ERR_WEIGHTS", -4: "PF_ERR_WORKSPACE"}
 
 # every symbol include/pf_hip.h declares: name -> (restype, argtypes)
