@@ -552,6 +552,49 @@ int pf_pano_rotate_ss(int device, int n_pano, const void* const* h_pano, const i
                       const int32_t* h_pano_index /*[batch]*/, const float* d_rot3 /*[batch][3] roll, pitch, yaw, radians*/, int inverse, int H, int W,
                       void* d_img /*[batch][H][W][3], dtype*/, float* d_up /*[batch][2][H][W]*/, float* d_lat /*[batch][H][W]*/, int samples, void* stream);
 
+/* Cube maps as a source: camera views and equirectangular panoramas out of six faces on the device (cube_gather.hip).
+ * THE CUBE-MAP CONVENTION.  A cube map is (6, N, N, 3), uint8 or fp32, channel-interleaved, N >= 1.  Face k is the picture of a pf_pano_crop pinhole
+ * camera with roll 0, rel_focal 1/2 (90 degrees), rel_cx = rel_cy = 0, xi = 0 and the (pitch, yaw) below, in the panorama's world frame (x right,
+ * y down, z towards longitude 0); its frame (right r, down d, forward n) is the columns of Y(yaw) R(0, pitch), an exact signed permutation:
+ *   k  name   pitch  yaw   r   d   n          k  name   pitch  yaw   r   d   n
+ *   0  front    0      0   +x  +y  +z         3  left     0    270   +z  +y  -x
+ *   1  right    0     90   -z  +y  +x         4  up     +90      0   +x  +z  -y
+ *   2  back     0    180   -x  +y  -z         5  down   -90      0   +x  -z  +y
+ * Texel (row, col) of face k has the direction n + a r + b d with a = 2 (col + 1/2) / N - 1, b = 2 (row + 1/2) / N - 1.
+ * The value of the cube in a direction X:
+ *   1 face      by the major axis: |z| >= |x| and |z| >= |y|: front (z >= 0) or back; else |x| >= |y|: right (x > 0) or left; else up (y < 0) or down
+ *   2 point     a = (X . r) / (X . n), b = (X . d) / (X . n); u = (a + 1) N / 2 - 1/2, v = (b + 1) N / 2 - 1/2, both in [-1/2, N - 1/2]
+ *   3 taps      rows (floor v, floor v + 1) x columns (floor u, floor u + 1), indices in [-1, N]; the indices -1 and N are the RING of the face
+ *   4 ring      a tap beyond the edge in face direction e in {+r, -r, +d, -d}, at the in-face coordinate t along the other axis o, is the texel of
+ *               the neighbouring face whose centre direction is e + (1 - 1/N) n + t o: the neighbour unfolded flat around the shared edge, the same
+ *               position along the edge, the first row or column inwards.  That is always a texel centre of the face whose forward axis is e
+ *   5 corner    a tap in the ring on both indices has no texel; its value is (T0 + Ta + Tb) * (1/3) in fp32, not rounded to the source's type: T0 the
+ *               face's own corner texel, Ta the ring texel beside it across the column edge, Tb across the row edge, summed in that order
+ *   6 blend     bilinear, the order of operations of the other gathers: top = (1 - fu) t00 + fu t01, bot likewise, (1 - fv) top + fv bot
+ * This sampler is continuous over the whole sphere, the 12 edges and 8 corners included: a view that straddles an edge has no seam, which a
+ * per-face clamped sampler leaves.  It is not the panorama's bilinear surface: next to an edge the flat unfolding misplaces a ring texel by up to
+ * 1/N of a face along the edge.
+ * pf_cube_crop: views of cameras theta = d_cam7 row = {roll, pitch, yaw (RADIANS), rel_focal, rel_cx, rel_cy, xi}: the ray of pf_pano_crop's pixel
+ * (pinhole or Unified Spherical Model), X = Y(yaw) R(roll, pitch) ray, the cube's value in X.  A pixel without a ray is 0.  A non-finite
+ * parameter: the view is 0 and no load is issued for it.
+ * pf_cube_to_pano: equirectangular panoramas; pixel -> direction D and the rotation A = Q or Q^T of pf_pano_rotate (d_rot3, inverse), X = A D,
+ * the cube's value in X: a tilted cube map is levelled into a panorama in one pass.  Non-finite angles: the output is 0, no load.
+ * Both: `samples` = S in 1 ... PF_GATHER_MAX_SAMPLES under the rule of the supersampled gathers above: every pixel is the mean of the S x S
+ * sub-samples at (col + (j + 1/2)/S, row + (i + 1/2)/S) that are valid (pf_cube_crop: that have a ray), the fp32 sum i-major then j divided by
+ * their count, 0 without one; S = 1 is the pixel centre.  PF_PANO_U8: the fp32 value rounded half up, clamped to [0, 255].  There are no labels:
+ * the fields of a view or of a panoramic camera do not depend on the source (pf_fields_from_params, pf_pano_fields).
+ * h_cube = HOST array of n_cube DEVICE pointers to (6, N, N, 3) of type `dtype`; h_cube_hw = HOST [n_cube][2] (N, N), N >= 1; h_cube_index = HOST
+ * [batch], the cube of each output.  d_img = DEVICE [batch][H][W][3] of `dtype`.  Argument errors (`samples` out of range, faces that are not
+ * square, NULL required pointers, n_cube < 1, batch < 1, N < 1, H or W < 1, a bad dtype, an index out of range) return PF_ERR_ARG before any
+ * device work with a message that begins with the function's name.  One launch per 32 outputs on `stream`, no workspace, no host
+ * synchronisation; stateless, no handle; deterministic, each output's bits independent of the batch it is in. */
+int pf_cube_crop(int device, int n_cube, const void* const* h_cube, const int32_t* h_cube_hw /*[n_cube][2]*/, int dtype /*PF_PANO_U8|PF_PANO_F32*/,
+                 int batch, const int32_t* h_cube_index /*[batch]*/, const float* d_cam7 /*[batch][7]*/, int H, int W,
+                 void* d_img /*[batch][H][W][3], dtype*/, int samples, void* stream);
+int pf_cube_to_pano(int device, int n_cube, const void* const* h_cube, const int32_t* h_cube_hw /*[n_cube][2]*/, int dtype, int batch,
+                    const int32_t* h_cube_index /*[batch]*/, const float* d_rot3 /*[batch][3] roll, pitch, yaw, radians*/, int inverse, int H, int W,
+                    void* d_img /*[batch][H][W][3], dtype*/, int samples, void* stream);
+
 /* The relative yaw of camera views of one centre, from the pictures: for ordered pairs (a, b) of views and a list of candidate turns, the moments of
  * the two luminance images on their overlap, from which the zero-mean normalised cross-correlation follows (yaw_align.hip).
  * The fields give roll, pitch and intrinsics of a view but not the direction it faces; with those known, two views of one centre differ by a single

@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -170,6 +170,41 @@ int pf_pano_rotate_ss(int device, int n_pano, const void* const* pano, const int
                       rb.rot = d_rot3 + (size_t)i0 * 3;
                       rb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
                       rb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
+                    });
+}
+
+// Cube maps as the source (cube_gather.hip): `samples`, then that every cube is square, then gather_run's checks with the source size (N, N)
+static bool cubes_square(const char* name, int n_cube, const int32_t* cube_hw) {
+  for (int k = 0; cube_hw && k < n_cube; ++k)
+    if (cube_hw[2 * k] != cube_hw[2 * k + 1]) {
+      g_create_error = fmt("%s: cube %d has faces of %d x %d, they must be square", name, k, cube_hw[2 * k], cube_hw[2 * k + 1]);
+      return false;
+    }
+  return true;
+}
+
+int pf_cube_crop(int device, int n_cube, const void* const* cube, const int32_t* cube_hw, int dtype, int B, const int32_t* cube_index, const float* d_cam7,
+                 int H, int W, void* d_img, int samples, void* stream) {
+  static const GatherKind kind{"pf_cube_crop", "cube", "view", 1, "needs at least one cube (h_cube, h_cube_hw)",
+                               "batch >= 1, h_cube_index, d_cam7 and d_img are required"};
+  if (!samples_ok(kind.name, samples) || !cubes_square(kind.name, n_cube, cube_hw)) return PF_ERR_ARG;
+  return gather_run(kind, launch_cube_crop, device, n_cube, cube, cube_hw, dtype, B, cube_index, d_cam7 != nullptr, H, W, d_img, nullptr, 0, stream,
+                    [=](CubeCropBatch& cb, int i0) {
+                      cb.samples = samples;
+                      cb.cam = d_cam7 + (size_t)i0 * 7;
+                    });
+}
+
+int pf_cube_to_pano(int device, int n_cube, const void* const* cube, const int32_t* cube_hw, int dtype, int B, const int32_t* cube_index, const float* d_rot3,
+                    int inverse, int H, int W, void* d_img, int samples, void* stream) {
+  static const GatherKind kind{"pf_cube_to_pano", "cube", "output", 1, "needs at least one cube (h_cube, h_cube_hw)",
+                               "batch >= 1, h_cube_index, d_rot3 and d_img are required"};
+  if (!samples_ok(kind.name, samples) || !cubes_square(kind.name, n_cube, cube_hw)) return PF_ERR_ARG;
+  return gather_run(kind, launch_cube_to_pano, device, n_cube, cube, cube_hw, dtype, B, cube_index, d_rot3 != nullptr, H, W, d_img, nullptr, 0, stream,
+                    [=](CubePanoBatch& cb, int i0) {
+                      cb.samples = samples;
+                      cb.inverse = inverse ? 1 : 0;
+                      cb.rot = d_rot3 + (size_t)i0 * 3;
                     });
 }
 

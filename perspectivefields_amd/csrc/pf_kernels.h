@@ -551,6 +551,30 @@ static_assert(offsetof(PanoSsBatch, samples) == 28 && offsetof(PanoSsBatch, src)
 static_assert(offsetof(ReprojSsBatch, samples) == 28 && offsetof(ReprojSsBatch, src) == 32, "ReprojSsBatch layout");
 static_assert(offsetof(PanoRotSsBatch, samples) == 28 && offsetof(PanoRotSsBatch, src) == 32, "PanoRotSsBatch layout");
 
+// cube maps -> camera views and equirectangular panoramas (cube_gather.hip, include/pf_hip.h pf_cube_crop / pf_cube_to_pano): the sources are cubes
+// (6, N, N, 3), src.H = src.W = N; `samples` as in the supersampled gathers
+struct CubeCropBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int samples;        // S in [1, PF_GATHER_MAX_SAMPLES]
+  GatherSources src;  // the cubes
+  const float* cam;   // [n][7], as PanoBatch
+  void* img;          // [n][H][W][3], the cubes' type
+};
+void launch_cube_crop(const CubeCropBatch& cb, int dtype, hipStream_t s);
+struct CubePanoBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int samples;
+  GatherSources src;  // the cubes
+  int inverse;        // as PanoRotBatch
+  const float* rot;   // [n][3]: roll, pitch, yaw (radians)
+  void* img;
+};
+void launch_cube_to_pano(const CubePanoBatch& cb, int dtype, hipStream_t s);
+static_assert(offsetof(CubeCropBatch, samples) == 28 && offsetof(CubeCropBatch, src) == 32, "CubeCropBatch layout");
+static_assert(offsetof(CubePanoBatch, samples) == 28 && offsetof(CubePanoBatch, src) == 32, "CubePanoBatch layout");
+
 // camera views of one centre -> equirectangular panoramas (pano_compose.hip, include/pf_hip.h pf_pano_compose): the outputs of a launch are up to MAX
 // panoramas, its sources up to MAX views; panorama k blends the views [first[k], first[k] + count[k]) of the launch in that order
 struct ComposeBatch {

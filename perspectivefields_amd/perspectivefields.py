@@ -1766,6 +1766,189 @@ def panorama_fields(roll, pitch, *, height, width, mode="deg", device=None):
     return up, lat
 
 
+_CUBE_FACES = ("front", "right", "back", "left", "up", "down")
+_CUBE_PITCH_YAW = ((0.0, 0.0), (0.0, 90.0), (0.0, 180.0), (0.0, 270.0), (90.0, 0.0), (-90.0, 0.0))   # include/pf_hip.h, the cube-map convention
+_CUBE_CROSS = ((1, 1), (1, 2), (1, 3), (1, 0), (0, 1), (2, 1))   # (block row, block column) of face k in the "cross" layout
+
+
+def cubemap_face_cameras(mode="deg"):
+    """The six cameras whose pictures are the faces front, right, back, left, up, down of a cube map (include/pf_hip.h, the cube-map convention):
+    a dict of per-face lists roll, pitch, yaw (degrees, radians with mode="rad") and rel_focal = 0.5, the parameters `crop_panorama` and
+    `compose_panorama` take: compose_panorama(faces, cubemap_face_cameras(), ...) turns six faces into a panorama by blending views,
+    crop_panorama(pano, **cubemap_face_cameras(), height=N, width=N) cuts them."""
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    conv = (lambda a: a) if mode == "deg" else (lambda a: float(np.radians(a)))
+    return dict(roll=[0.0] * 6, pitch=[conv(p) for p, _ in _CUBE_PITCH_YAW], yaw=[conv(y) for _, y in _CUBE_PITCH_YAW], rel_focal=[0.5] * 6)
+
+
+def _cube_list(fn, cube):
+    """the cube maps of a gather: (6, N, N, 3) CUDA tensors of one dtype and one device -> (list, device)"""
+    cubes, dev = _cuda_image_list(fn, [cube] if torch.is_tensor(cube) else list(cube), ("cube map", "cube maps"),
+                                  "a cube map must be (6, N, N, 3) with N >= 1", 1, ndim=4)
+    for c in cubes:
+        if c.shape[0] != 6 or c.shape[1] != c.shape[2]:
+            raise ValueError(f"a cube map must be (6, N, N, 3) with N >= 1; got {tuple(c.shape)}")
+    return cubes, dev
+
+
+def _cube_index(cube_index, B, n, what):
+    if cube_index is None:
+        return [0] * B
+    idx = [operator.index(i) for i in (cube_index.tolist() if torch.is_tensor(cube_index) else cube_index)]
+    if len(idx) != B:
+        raise ValueError(f"cube_index has {len(idx)} entries for {B} {what}")
+    if any(i < 0 or i >= n for i in idx):
+        raise ValueError(f"cube_index entries must be in [0, {n})")
+    return idx
+
+
+def crop_cubemap(cube, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0.0, xi=0.0, height, width, cube_index=None, mode="deg", fields=True, samples=1):
+    """Cube maps -> camera views and their ground-truth perspective fields on the GPU: `crop_panorama` for 360 degree material stored as six faces
+    (skyboxes, environment maps, six-face camera exports), without a detour through a panorama.  Convention and sampling: include/pf_hip.h
+    pf_cube_crop.
+
+    cube: a CUDA tensor (6, N, N, 3), uint8 or float32, faces front, right, back, left, up, down (`cubemap_face_cameras`), or a list of them (one
+    dtype, one device; N may differ).  The camera parameters, mode, height, width and samples are `crop_panorama`'s; cube_index: None (every view
+    from cube 0) or B integers.  The bilinear sampler is continuous across the edges and corners of the cube: a view that straddles an edge has no
+    seam.  Returns (images (B, H, W, 3) in the cube's dtype, up (B, 2, H, W), lat (B, H, W) degrees); up / lat are `fields_from_params` of the same
+    parameters (they do not depend on the source) and None with fields=False.  Pixels without a ray (xi > 1) are 0; a view with a non-finite
+    parameter is 0.  GPU only: CPU cubes raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    fn = "crop_cubemap"
+    samples = _check_samples(fn, samples)
+    cubes, dev = _cube_list(fn, cube)
+    H, W = int(height), int(width)
+    if H < 1 or W < 1:
+        raise ValueError(f"view size must be at least 1 x 1; got {H} x {W}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    ts = _rotation_params(fn, (("roll", roll), ("pitch", pitch), ("yaw", yaw), ("rel_focal", rel_focal), ("rel_cx", rel_cx), ("rel_cy", rel_cy), ("xi", xi)))
+    B = _broadcast_len(fn, ts)
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one view")
+    idx = _cube_index(cube_index, B, len(cubes), "views")
+    cam = _camera_rows(ts, (0, 1, 2), B, dev, mode).contiguous()
+    cubes = [c.contiguous() for c in cubes]
+    img = torch.empty((B, H, W, 3), dtype=cubes[0].dtype, device=dev)
+    p_cube, hw, c_idx = _source_arrays(cubes, [(int(c.shape[1]), int(c.shape[2])) for c in cubes], idx)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_cube_crop(dev.index, len(cubes), p_cube, hw, _PANO_DTYPES[cubes[0].dtype], B, c_idx, cam.data_ptr(), H, W, img.data_ptr(), samples,
+                                _stream_ptr()), None, "pf_cube_crop")
+    if not fields:
+        return img, None, None
+    pinhole = not torch.is_tensor(xi) and np.ndim(xi) == 0 and float(xi) == 0.0   # fields_from_params' rule: the number 0 is the pinhole model
+    rows = [t.expand(B) for t in ts]
+    per_view = [fields_from_params(rows[0][i], rows[1][i], rows[3][i], rows[4][i], rows[5][i], height=H, width=W, mode=mode, device=dev,
+                                   xi=0.0 if pinhole else rows[6][i]) for i in range(B)]
+    return img, torch.stack([u for u, _ in per_view]), torch.stack([l for _, l in per_view])
+
+
+def cubemap_to_panorama(cube, *, height, width, roll=0.0, pitch=0.0, yaw=0.0, inverse=False, cube_index=None, mode="deg", fields=False, samples=1):
+    """Cube maps -> equirectangular panoramas on the GPU, turned on the way if angles are given: a tilted cube map is levelled into a panorama in one
+    pass.  Convention and sampling: include/pf_hip.h pf_cube_to_pano.
+
+    cube: as `crop_cubemap`.  roll, pitch, yaw, inverse, mode, samples: `rotate_panorama`'s, with the cube in the place of the source panorama
+    (inverse=False: what a panoramic camera with that orientation inside the cube sees; inverse=True: a cube shot by such a rig becomes upright).
+    height, width: the size of every output; cube_index: None (every output from cube 0) or B integers.
+    Returns the images (B, H, W, 3) in the cube's dtype; with fields=True (images, up, lat), the fields being `panorama_fields(roll, pitch)` (those
+    of the output's camera for inverse=False).  Non-finite angles give an image of 0.  GPU only: CPU cubes raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    fn = "cubemap_to_panorama"
+    samples = _check_samples(fn, samples)
+    cubes, dev = _cube_list(fn, cube)
+    H, W = int(height), int(width)
+    if H < 1 or W < 1:
+        raise ValueError(f"output size must be at least 1 x 1; got {H} x {W}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    ts = _rotation_params(fn, (("roll", roll), ("pitch", pitch), ("yaw", yaw)))
+    B = _broadcast_len(fn, ts)
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one output")
+    idx = _cube_index(cube_index, B, len(cubes), "outputs")
+    rot = _camera_rows(ts, (0, 1, 2), B, dev, mode).contiguous()
+    cubes = [c.contiguous() for c in cubes]
+    img = torch.empty((B, H, W, 3), dtype=cubes[0].dtype, device=dev)
+    p_cube, hw, c_idx = _source_arrays(cubes, [(int(c.shape[1]), int(c.shape[2])) for c in cubes], idx)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_cube_to_pano(dev.index, len(cubes), p_cube, hw, _PANO_DTYPES[cubes[0].dtype], B, c_idx, rot.data_ptr(), 1 if inverse else 0, H, W,
+                                   img.data_ptr(), samples, _stream_ptr()), None, "pf_cube_to_pano")
+    if not fields:
+        return img
+    up, lat = panorama_fields(ts[0].expand(B), ts[1].expand(B), height=H, width=W, mode=mode, device=dev)
+    return img, up, lat
+
+
+def panorama_to_cubemap(pano, size, *, roll=0.0, pitch=0.0, yaw=0.0, samples=1):
+    """Equirectangular panoramas -> cube maps on the GPU: the six `crop_panorama` views of `cubemap_face_cameras()` at size x size, bit for bit.
+    pano: a CUDA tensor (Hp, Wp, 3), uint8 or float32, or a list of B of them.  roll, pitch, yaw (degrees; numbers or B values): when one is given the
+    panorama is first turned by `rotate_panorama` with these angles (the cube of a rig with that orientation inside the panorama), one more
+    bilinear resampling.  samples: `crop_panorama`'s antialiasing of the faces.  Returns (B, 6, N, N, 3) in the panorama's dtype, faces front, right,
+    back, left, up, down.  GPU only: CPU panoramas raise PfError."""
+    fn = "panorama_to_cubemap"
+    samples = _check_samples(fn, samples)
+    panos, _ = _cuda_image_list(fn, [pano] if torch.is_tensor(pano) else list(pano), ("panorama", "panoramas"),
+                                "a panorama must be (Hp, Wp, 3) with Hp, Wp >= 2", 2)
+    N = operator.index(size)
+    if N < 1:
+        raise ValueError(f"{fn}: size must be at least 1; got {N}")
+    ts = _rotation_params(fn, (("roll", roll), ("pitch", pitch), ("yaw", yaw)))
+    B = len(panos)
+    if _broadcast_len(fn, ts) not in (1, B) or any(t.dim() == 1 and t.shape[0] not in (1, B) for t in ts):
+        raise ValueError(f"{fn}: roll, pitch and yaw are numbers or one value per panorama ({B})")
+    if any(torch.is_tensor(v) or np.any(np.asarray(v) != 0) for v in (roll, pitch, yaw)):
+        panos = [rotate_panorama(p, *(t if t.dim() == 0 else t[i % t.shape[0]] for t in ts))[0] for i, p in enumerate(panos)]
+    cams = cubemap_face_cameras()
+    faces, _, _ = crop_panorama(panos, cams["roll"] * B, cams["pitch"] * B, cams["rel_focal"] * B, yaw=cams["yaw"] * B, height=N, width=N,
+                                pano_index=[i for i in range(B) for _ in range(6)], fields=False, samples=samples)
+    return faces.view(B, 6, N, N, 3)
+
+
+def _cube_layout(fn, layout):
+    if layout not in ("strip", "cross"):
+        raise ValueError(f"{fn}: layout must be 'strip' or 'cross'; got {layout!r}")
+
+
+def cubemap_to_image(cube, layout):
+    """A cube map (..., 6, N, N, 3) as one picture in an on-disk layout, by slicing alone (any device, any dtype): "strip" (..., N, 6 N, 3), faces
+    0 ... 5 left to right; "cross" (..., 3 N, 4 N, 3), up at block (row 0, column 1), left, front, right, back at (1, 0 ... 3), down at (2, 1), the
+    rest 0.  `cubemap_from_image` is the exact inverse."""
+    fn = "cubemap_to_image"
+    _cube_layout(fn, layout)
+    if not torch.is_tensor(cube) or cube.dim() < 4 or cube.shape[-4] != 6 or cube.shape[-1] != 3 or cube.shape[-2] != cube.shape[-3] or cube.shape[-2] < 1:
+        raise ValueError(f"{fn}: a cube map is a tensor (..., 6, N, N, 3) with N >= 1; got {tuple(cube.shape) if torch.is_tensor(cube) else type(cube)}")
+    N = cube.shape[-2]
+    if layout == "strip":
+        return torch.cat([cube[..., k, :, :, :] for k in range(6)], dim=-2)
+    img = cube.new_zeros(tuple(cube.shape[:-4]) + (3 * N, 4 * N, 3))
+    for k, (br, bc) in enumerate(_CUBE_CROSS):
+        img[..., br * N:(br + 1) * N, bc * N:(bc + 1) * N, :] = cube[..., k, :, :, :]
+    return img
+
+
+def cubemap_from_image(img, layout):
+    """The cube map (..., 6, N, N, 3) of a picture (..., H, W, 3) in the layout "strip" (W = 6 H) or "cross" (H = 3 N, W = 4 N): `cubemap_to_image`'s
+    inverse, by slicing alone; the blocks of a cross that hold no face are ignored."""
+    fn = "cubemap_from_image"
+    _cube_layout(fn, layout)
+    if not torch.is_tensor(img) or img.dim() < 3 or img.shape[-1] != 3:
+        raise ValueError(f"{fn}: a picture is a tensor (..., H, W, 3); got {tuple(img.shape) if torch.is_tensor(img) else type(img)}")
+    H, W = img.shape[-3], img.shape[-2]
+    if layout == "strip":
+        if H < 1 or W != 6 * H:
+            raise ValueError(f"{fn}: a strip is (N, 6 N, 3); got {H} x {W}")
+        return torch.stack([img[..., :, k * H:(k + 1) * H, :] for k in range(6)], dim=-4)
+    N = H // 3
+    if N < 1 or H != 3 * N or W != 4 * N:
+        raise ValueError(f"{fn}: a cross is (3 N, 4 N, 3); got {H} x {W}")
+    return torch.stack([img[..., br * N:(br + 1) * N, bc * N:(bc + 1) * N, :] for br, bc in _CUBE_CROSS], dim=-4)
+
+
 def _rot_roll_pitch(roll, pitch):
     """R = R_pitch(pitch) R_roll(roll), camera -> world, for fp64 tensors (..., ) of radians -> (..., 3, 3)"""
     cr, sr, cp, sp = torch.cos(roll), torch.sin(roll), torch.cos(pitch), torch.sin(pitch)
