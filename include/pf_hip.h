@@ -765,6 +765,49 @@ int pf_draw_fields(int device, int batch, const int32_t* h_hw /*[batch][2]*/, co
                    float lat_step_deg, float alpha, float line_width, const float* h_arrow_rgb /*[3]*/, int layers /*PF_DRAW_UP|PF_DRAW_LAT*/,
                    void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* Objects pasted into background pictures on the device: the object's pixels under pf_fields_transform's similarity, alpha-blended into the
+ * background at a placement that is read from device memory (composite.hip).  What pf_place_search finds can be pasted
+ * without a host synchronisation in between.
+ *   images     channel-interleaved [H][W][3], uint8 or fp32 on the 0 - 255 scale (pf_draw_fields' pictures); backgrounds, objects and outputs of one
+ *              dtype.  An object's alpha is an [h][w] fp32 plane; a NULL plane is opaque; a value is clamped to [0, 1] and NaN is 0.
+ *   jobs       job k = background h_jobs[k][0], object h_jobs[k][1], output h_out[k] of the background's size, and the row
+ *              d_place[k] = (s, phi in degrees, row, col, h', w'), six fp64 values in DEVICE memory.  (s, phi) is a variant of pf_fields_transform;
+ *              (row, col) is where the top-left corner of the transformed object's h' x w' box lies in the background (pf_place_search's offset); it
+ *              may be negative and the box may hang over the border: the paste is clipped to the background.  A row is INACTIVE when s is not finite
+ *              and > 0; phi, row or col is not finite; row or col is not integer-valued or is 2^30 or more in magnitude; h' or w' is < 1, not
+ *              integer-valued, or 2^31 or more.  An inactive row gives the background's bits and coverage 0.
+ *   sampling   output pixel (R, C), r' = R - row, c' = C - col.  Outside [0, h') x [0, w'): the background's bits, coverage 0.  Inside, for the
+ *              sub-samples a, b < S = `samples`, a-major (the order of the supersampled gathers): d = (c' + (b + 1/2) / S - w'/2,
+ *              r' + (a + 1/2) / S - h'/2) with (b + 1/2) / S an fp32 quotient, source position (x, y) = (w/2, h/2) + R(-phi) d / s - (1/2, 1/2),
+ *              in fp32 with pf_fields_transform's operations; four bilinear taps at floor(x), floor(y) and their + 1 neighbours.  A tap outside the
+ *              array is TRANSPARENT -- it counts as alpha 0 and is not dropped and renormalised --, a tap whose alpha is 0 is skipped, so that what
+ *              lies under a zero alpha, NaN included, never reaches the output.  A_ab = sum w_k alpha_k and P_ab = sum (w_k alpha_k) c_k per
+ *              channel, in fp64 from the fp32 weights w_k; A and P are the means over the S x S sub-samples.
+ *   cos, sin   of phi in fp64 from remainder(phi, 360), exactly 0 or +-1 at the multiples of 90, and 1 / s: computed once per job on the device
+ *              and rounded to fp32 once.
+ *   edge       PF_COMPOSITE_SOFT: cov = opacity A, out = bg (1 - cov) + opacity P.
+ *              PF_COMPOSITE_HARD: where A >= 1/2, cov = opacity and out = bg (1 - opacity) + opacity P / A; elsewhere cov = 0 -- the silhouette that
+ *              pf_fields_transform keeps, so the pasted pixels are the pixels the search scored.
+ *              Where cov = 0 the output is the background's bits.
+ *   blend      in fp64, rounded once: fp32 outputs by one rounding, uint8 outputs half up and clamped to [0, 255].
+ * h_bg, h_obj = HOST arrays of n_bg, n_obj (>= 1) DEVICE pointers; h_obj_alpha = NULL (every object opaque) or a HOST array of n_obj DEVICE pointers
+ * whose entries may be NULL; h_bg_hw, h_obj_hw = HOST [.][2] (H, W), each >= 1, H W < 2^31; dtype PF_PANO_U8 | PF_PANO_F32; h_jobs = HOST [n][2]; h_out =
+ * HOST array of n DEVICE pointers, every job its own image, none of them a background; d_cov = NULL or DEVICE fp32, the coverage planes of
+ * the jobs one after another, job k's of its background's size; workspace of pf_composite_workspace_bytes(n) (0 for n < 1): one record per job.
+ * Argument errors (counts < 1, NULL arrays or pointers, a side < 1 or 2^31 pixels or more, a job index out of range, samples outside
+ * 1 ... PF_GATHER_MAX_SAMPLES, opacity outside [0, 1] or not finite, an unknown edge or dtype, a small workspace, an output that is its background or another job's or is shared by two jobs,
+ * fp32 data not aligned to 4 bytes, d_place not to 8) return PF_ERR_ARG before any device work.  Two launches per 32 jobs on `stream`, no atomics, no
+ * host-to-device copy, no host synchronisation; stateless, no handle.  Every output pixel depends on its own job only: the same bits in any batch, in
+ * any order of the jobs and on every run. */
+#define PF_COMPOSITE_SOFT 0
+#define PF_COMPOSITE_HARD 1
+size_t pf_composite_workspace_bytes(int n);
+int pf_composite(int device, int n_bg, const void* const* h_bg, const int32_t* h_bg_hw /*[n_bg][2]*/, int n_obj, const void* const* h_obj,
+                 const float* const* h_obj_alpha /*entries may be NULL*/, const int32_t* h_obj_hw /*[n_obj][2]*/, int dtype /*PF_PANO_U8|PF_PANO_F32*/, int n,
+                 const int32_t* h_jobs /*[n][2]: (background, object)*/, const double* d_place /*[n][6]: s, phi, row, col, h', w'*/, double opacity,
+                 int edge /*PF_COMPOSITE_SOFT|PF_COMPOSITE_HARD*/, int samples, void* const* h_out /*n device pointers*/, float* d_cov /*[n] planes or NULL*/,
+                 void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* Predicted perspective fields against ground truth on the device: per-pixel errors, per-image statistics with an exact median, and
  * a running histogram for dataset statistics (field_err.hip).
  * Inputs per image: up_pred, up_gt [2][H][W] and lat_pred, lat_gt [H][W] degrees, fp32 (the layout of pred_gravity_original /

@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the pasting of objects (composite.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -853,6 +853,74 @@ int pf_draw_fields(int device, int B, const int32_t* hw, const void* const* img,
     launch_draw_fields(db, dtype, s);
   }
   if (hipGetLastError() != hipSuccess) { g_create_error = "pf_draw_fields: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+// pf_composite (composite.hip): workspace = a CompositeJob record per job, 256-byte aligned
+size_t pf_composite_workspace_bytes(int n) { return n < 1 ? 0 : 256 + yaw_align((size_t)n * sizeof(CompositeJob)); }
+
+int pf_composite(int device, int n_bg, const void* const* bg, const int32_t* bg_hw, int n_obj, const void* const* obj, const float* const* obj_alpha,
+                 const int32_t* obj_hw, int dtype, int n, const int32_t* jobs, const double* d_place, double opacity, int edge, int samples, void* const* out,
+                 float* d_cov, void* ws, size_t ws_bytes, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_composite: " + m; return PF_ERR_ARG; };
+  if (n_bg < 1 || n_obj < 1 || n < 1) return bad(fmt("n_bg %d, n_obj %d and n %d must be >= 1", n_bg, n_obj, n));
+  if (!bg || !bg_hw || !obj || !obj_hw || !jobs || !d_place || !out) return bad("h_bg, h_bg_hw, h_obj, h_obj_hw, h_jobs, d_place and h_out are required");
+  if (dtype != PF_PANO_U8 && dtype != PF_PANO_F32) return bad(fmt("unknown dtype %d", dtype));
+  if (edge != PF_COMPOSITE_SOFT && edge != PF_COMPOSITE_HARD) return bad(fmt("unknown edge %d", edge));
+  if (!samples_ok("pf_composite", samples)) return PF_ERR_ARG;
+  if (!(opacity >= 0.0 && opacity <= 1.0)) return bad(fmt("opacity %g, must be in [0, 1]", opacity));
+  const uintptr_t elem = dtype == PF_PANO_U8 ? 0 : 3;
+  for (int pass = 0; pass < 2; ++pass) {
+    const int cnt = pass ? n_obj : n_bg;
+    const int32_t* hw = pass ? obj_hw : bg_hw;
+    const void* const* im = pass ? obj : bg;
+    const char* what = pass ? "object" : "background";
+    for (int i = 0; i < cnt; ++i) {
+      const int H = hw[2 * i], W = hw[2 * i + 1];
+      if (H < 1 || W < 1 || (long long)H * W > INT32_MAX) return bad(fmt("%s %d is %d x %d, smaller than 1 x 1 or of 2^31 pixels or more", what, i, H, W));
+      if (!im[i]) return bad(fmt("NULL pointer of %s %d", what, i));
+      if (misalign(im[i], elem) || (pass && obj_alpha && misalign(obj_alpha[i], 3))) return bad(fmt("%s %d: fp32 images and alpha planes must be aligned to 4 bytes", what, i));
+    }
+  }
+  if (misalign(d_place, 7) || misalign(d_cov, 3)) return bad("d_place must be aligned to 8 bytes and d_cov to 4");
+  for (int k = 0; k < n; ++k) {
+    const int b = jobs[2 * k], o = jobs[2 * k + 1];
+    if (b < 0 || b >= n_bg || o < 0 || o >= n_obj) return bad(fmt("job %d: index (%d, %d) out of range, %d backgrounds and %d objects", k, b, o, n_bg, n_obj));
+    if (!out[k]) return bad(fmt("NULL output pointer of job %d", k));
+    if (misalign(out[k], elem)) return bad(fmt("job %d: an fp32 output must be aligned to 4 bytes", k));
+    if (out[k] == bg[b]) return bad(fmt("job %d: the output is its background; in-place composition is not offered", k));
+    for (int f = 0; f < n_bg; ++f)
+      if (out[k] == bg[f]) return bad(fmt("job %d: the output is background %d, which another job may be reading", k, f));
+  }
+  std::vector<const void*> sorted(out, out + n);  // two jobs never share an output: no order between them is defined
+  std::sort(sorted.begin(), sorted.end());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return bad("two jobs share an output");
+  const size_t need = pf_composite_workspace_bytes(n);
+  if (!ws || ws_bytes < need) return bad(fmt("needs %zu workspace bytes, got %zu", need, ws_bytes));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uintptr_t mask = dtype == PF_PANO_U8 ? 3 : 15;
+  float* cov = d_cov;
+  for (int k0 = 0; k0 < n; k0 += CompositeBatch::MAX) {
+    CompositeBatch cb;
+    cb.n = std::min(n - k0, (int)CompositeBatch::MAX);
+    cb.first = k0; cb.samples = samples; cb.hard = edge == PF_COMPOSITE_HARD ? 1 : 0; cb.opacity = opacity;
+    cb.place = d_place;
+    cb.rec = reinterpret_cast<CompositeJob*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+    for (int k = 0; k < cb.n; ++k) {
+      const int b = jobs[2 * (k0 + k)], o = jobs[2 * (k0 + k) + 1];
+      cb.H[k] = bg_hw[2 * b]; cb.W[k] = bg_hw[2 * b + 1]; cb.h[k] = obj_hw[2 * o]; cb.w[k] = obj_hw[2 * o + 1];
+      cb.bg[k] = bg[b]; cb.obj[k] = obj[o]; cb.alpha[k] = obj_alpha ? obj_alpha[o] : nullptr; cb.out[k] = out[k0 + k];
+      cb.cov[k] = cov;
+      cb.vec[k] = (misalign(bg[b], mask) | misalign(out[k0 + k], mask)) == 0 ? 1 : 0;
+      cb.cvec[k] = misalign(cov, 15) == 0 ? 1 : 0;
+      if (cov) cov += (size_t)cb.H[k] * cb.W[k];
+    }
+    launch_composite(cb, dtype, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_composite: kernel launch failed"; return PF_ERR_DEVICE; }
   return PF_OK;
 }
 

@@ -708,6 +708,34 @@ void launch_place_best_pairs(int n_pair, int n_var, int stride, const BestHead* 
                              hipStream_t s);
 static_assert(sizeof(FieldXform) <= 4096 && sizeof(BestCount) <= 4096 && sizeof(BestBatch) <= 4096, "FieldXform, BestCount and BestBatch fit the kernel arguments");
 
+// objects pasted into backgrounds (composite.hip, include/pf_hip.h pf_composite): up to CompositeBatch::MAX jobs per launch, a job's pointers and sizes
+// in the kernel arguments, its placement in a record that composite_prep_kernel writes from the caller's device table
+struct CompositeJob {      // one per job, in the workspace
+  int active;              // 0: the output is the background
+  float c, s, inv;         // cos phi, sin phi, 1 / scale: fp64 on the device, rounded once
+  int row, col, hb, wb;    // the box's top-left corner in the background and its size h', w'
+  int r0, r1, c0, c1;      // the box clipped to the background: rows [r0, r1), columns [c0, c1); empty for an inactive job
+};
+struct CompositeBatch {
+  static constexpr int MAX = 32;
+  int n, first;            // jobs of this launch; the first one's index in `place` and `rec`
+  int samples, hard;       // S; 1: PF_COMPOSITE_HARD
+  double opacity;
+  int H[MAX], W[MAX];      // background size
+  int h[MAX], w[MAX];      // object size
+  int vec[MAX];            // 1: background and output aligned for the 4-pixel accesses (uint8: 4 bytes, fp32: 16)
+  int cvec[MAX];           // 1: the coverage plane is aligned to 16 bytes
+  const void* bg[MAX];     // (H, W, 3) uint8 or fp32
+  const void* obj[MAX];    // (h, w, 3) of the same type
+  const float* alpha[MAX]; // (h, w) or NULL: opaque
+  void* out[MAX];          // (H, W, 3)
+  float* cov[MAX];         // (H, W) or NULL
+  const double* place;     // [jobs of the call][6]: s, phi, row, col, h', w'
+  CompositeJob* rec;       // [jobs of the call]
+};
+void launch_composite(const CompositeBatch& cb, int dtype, hipStream_t s);  // the records of the launch's jobs, then the pixels
+static_assert(sizeof(CompositeJob) == 48 && sizeof(CompositeBatch) <= 4096, "CompositeBatch fits the kernel arguments");
+
 // perspective fields drawn over their images (draw_fields.hip, include/pf_hip.h pf_draw_fields): up to DrawBatch::MAX images per launch, per-image sizes
 // and pointers in the kernel arguments
 struct DrawBatch {

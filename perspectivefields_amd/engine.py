@@ -89,6 +89,8 @@ _SIGNATURES = {
                                    _P, _c.c_size_t, _P, _P, _P, _c.c_size_t, _P]),
     "pf_draw_fields_workspace_bytes": (_c.c_size_t, [_c.c_int, _P, _c.c_int]),
     "pf_draw_fields": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_float, _P, _c.c_int, _P, _c.c_size_t, _P]),
+    "pf_composite_workspace_bytes": (_c.c_size_t, [_c.c_int]),
+    "pf_composite": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_double, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P]),
     "pf_field_errors_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
     "pf_field_errors": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_float, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
     "pf_profile_begin": (_c.c_int, [_P, _c.c_uint]),

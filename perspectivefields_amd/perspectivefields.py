@@ -523,6 +523,25 @@ class PerspectiveFields(nn.Module):
 
         return placement_search(*fields(pred_bg), *fields(pred_obj), **kw)
 
+    def composite(self, images_bg, images_obj, search, *, alpha=None, **kw):
+        """The pictures of a placement search pasted where the search put them, on the GPU: `search` is what placement_search / m.placement_search
+        returned (one dict, or the list with one dict per pair), images_bg and images_obj are the pictures whose fields were searched, of the
+        fields' sizes and in the arrangement the search took them in.  best_scale, best_rotation_deg, best_offset and best_size go into
+        composite_objects as the device tensors they are, so nothing is read back between search and paste; a pair for which nothing fitted
+        (best_variant -1) returns its background.  alpha: the objects' masks or mattes; see composite_objects for it and for the options --
+        pairs (the pairs the search was given), opacity, edge, samples, return_coverage -- and what is returned."""
+        res = [search] if isinstance(search, dict) else list(search)
+        if not res or not all(isinstance(d, dict) and {"best_scale", "best_rotation_deg", "best_offset", "best_size", "best_variant"} <= set(d) for d in res):
+            raise ValueError("composite: search must be the result of placement_search: a dict or a list of dicts with best_scale, best_rotation_deg, "
+                             "best_offset, best_size and best_variant")
+        nan = float("nan")
+        found = [d["best_variant"] >= 0 for d in res]
+        col = lambda key, i=None: torch.stack([torch.where(f, (d[key] if i is None else d[key][i]).to(torch.float64), torch.full_like(d["best_scale"], nan))
+                                               for d, f in zip(res, found)])
+        return composite_objects(images_bg, images_obj, scale=col("best_scale"), rotation=col("best_rotation_deg"),
+                                 offset=torch.stack([col("best_offset", 0), col("best_offset", 1)], 1),
+                                 size=torch.stack([col("best_size", 0), col("best_size", 1)], 1), alpha=alpha, **kw)
+
     def draw_fields(self, images, preds, **kw):
         """The dense fields of inference* results drawn over their pictures, on the GPU: one result dict for one image, or a list of them for a
         list of images or a (B, H, W, 3) tensor; see draw_perspective_fields for `images`, the options -- density, arrow_inv_len, lat_step_deg,
@@ -1443,6 +1462,165 @@ def placement_search(up_bg, lat_bg, up_obj, lat_obj, *, scales=(1.0,), rotations
             d["maps"] = ms
         res.append(d)
     return res[0] if single else res
+
+
+COMPOSITE_SOFT, COMPOSITE_HARD = 0, 1   # include/pf_hip.h PF_COMPOSITE_*
+_EDGES = {"soft": COMPOSITE_SOFT, "hard": COMPOSITE_HARD}
+
+
+def _placement_columns(fn, name, v, width, n):
+    """a per-job parameter of composite_objects -> (is a tensor, `width` columns): host numbers give lists of n floats, a device tensor gives float64
+    tensors of shape (n,) that were never read"""
+    if torch.is_tensor(v):
+        shape = tuple(v.shape)
+        ok = shape in ((), (n,)) if width == 1 else shape in ((width,), (n, width))
+        if not ok or v.dtype == torch.bool or v.is_complex():
+            raise ValueError(f"{fn}: {name} as a tensor is {'a number or (n,)' if width == 1 else f'({width},) or (n, {width})'} for n = {n} jobs; got {shape}")
+        t = v.to(torch.float64).reshape(-1, width).expand(n, width)
+        return True, [t[:, i] for i in range(width)]
+    try:
+        a = np.asarray(v, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: {name} must be numbers or a tensor; got {v!r}") from None
+    ok = a.shape in ((), (n,)) if width == 1 else a.shape in ((width,), (n, width))
+    if not ok:
+        raise ValueError(f"{fn}: {name} is {'a number or n numbers' if width == 1 else f'{width} numbers or n rows of them'} for n = {n} jobs; got shape {a.shape}")
+    a = np.broadcast_to(a.reshape(-1, width), (n, width))
+    return False, [[float(x) for x in a[:, i]] for i in range(width)]
+
+
+def composite_objects(backgrounds, objects, *, scale=1.0, rotation=0.0, offset, size=None, alpha=None, pairs=None, opacity=1.0, edge="soft", samples=1,
+                      return_coverage=False):
+    """Objects pasted into background pictures on the GPU: the object's pixels resized by `scale` and turned by `rotation` degrees about its centre
+    (transform_fields' similarity, so the pixels move as the fields did), alpha-blended into the background at `offset`.  It consumes what
+    placement_search finds -- its best_scale, best_rotation_deg, best_offset and best_size can be passed as the device tensors they are, and nothing is
+    read back.  Definitions: include/pf_hip.h pf_composite.
+
+    backgrounds, objects: a CUDA tensor (H, W, 3), a batch (B, H, W, 3), or a list of (H, W, 3) tensors whose sizes may differ; uint8 or float32 on the
+    0 - 255 scale, one dtype and one device for all.  An object may have 4 channels: colour and alpha on the 0 - 255 scale.  alpha: a bool or float
+    (h, w) tensor in [0, 1] (one, or a list with one entry per object, None entries allowed), None = opaque; NaN counts as 0.
+    pairs: (background, object) indices, one job each; default every background with every object, backgrounds outermost (placement_search's order).
+    Per job, as host numbers (one for all jobs or one per job) or as device tensors (0-d / (n,), offset and size (2,) / (n, 2)):
+    scale > 0; rotation in degrees, positive = clockwise on the screen; offset = (row, col) of the top-left corner of the transformed object's box in
+    the background, which may be negative or hang over the border (the paste is clipped); size = (h', w') of that box, default the size
+    transform_fields gives, which needs scale and rotation as host numbers: with tensors pass size=.  A job whose values cannot be pasted -- a scale
+    that is not finite and > 0, a non-finite rotation, an offset that is not integer-valued, a size below 1 (placement_search's "nothing fits") --
+    returns its background unchanged.
+    opacity in [0, 1] multiplies the alpha.  edge="soft": the premultiplied bilinear mix, the object's outline and the array border fade over a pixel;
+    edge="hard": a pixel is pasted in full where the resampled alpha is at least 1/2 and not at all elsewhere -- transform_fields' silhouette, the
+    pixels the search scored.  samples=S in 1 .. 4: every pixel is the mean of S x S sub-samples (antialiasing for scale < 1), as for the gathers.
+    Returns the composites: (H, W, 3) for one background tensor and one object tensor, (n, H, W, 3) for one background or a batch of them, a list for
+    a list; with return_coverage also the coverage in [0, 1], float32, (H, W) per job in the same arrangement.  A pixel that is not covered keeps
+    the background's bits.  uint8 results are rounded half up.  One C call on the current stream, no host synchronisation.  Deterministic; a
+    job's bits do not depend on the other jobs.  GPU only: CPU tensors raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    fn = "composite_objects"
+    kind_b, bgs = _draw_images(fn, backgrounds)
+    kind_o, objs = _draw_images(fn, objects)
+    if not all(torch.is_tensor(t) for t in bgs + objs):
+        raise TypeError(f"{fn} takes torch tensors")
+    for what, kind, ts, chans in (("a background", kind_b, bgs, (3,)), ("an object", kind_o, objs, (3, 4))):
+        for t in ts:
+            if t.dim() != (4 if kind == "batched" else 3) or t.shape[-1] not in chans or min(t.shape[-3:-1]) < 1 or (kind == "batched" and t.shape[0] < 1):
+                raise ValueError(f"{fn}: {what} must be (H, W, {' or '.join(map(str, chans))}) with H, W >= 1, or a non-empty batch of them; got {tuple(t.shape)}")
+            if t.dtype not in _PANO_DTYPES:
+                raise ValueError(f"{fn}: images must be uint8 or float32; got {t.dtype}")
+    if not bgs or not objs:
+        raise ValueError(f"{fn} needs at least one background and one object")
+    if len({t.dtype for t in bgs + objs}) != 1:
+        raise ValueError(f"{fn}: backgrounds and objects must have one dtype")
+    bgs = list(bgs[0].unbind(0)) if kind_b == "batched" else bgs
+    objs = list(objs[0].unbind(0)) if kind_o == "batched" else objs
+    if len({o.shape[-1] for o in objs}) != 1:
+        raise ValueError(f"{fn}: the objects must all have 3 or all have 4 channels")
+    nb, no = len(bgs), len(objs)
+    if objs[0].shape[-1] == 4:
+        if alpha is not None:
+            raise ValueError(f"{fn}: alpha= with 4-channel objects, which carry their own")
+        alphas = [o[..., 3].to(torch.float32) / 255.0 for o in objs]
+        objs = [o[..., :3] for o in objs]
+    else:
+        alphas = [None] * no if alpha is None else [alpha] if torch.is_tensor(alpha) else list(alpha)
+        if len(alphas) != no:
+            raise ValueError(f"{fn}: {len(alphas)} alpha planes for {no} objects")
+        for a, o in zip(alphas, objs):
+            if a is not None and (not torch.is_tensor(a) or tuple(a.shape) != tuple(o.shape[:2]) or not (a.dtype == torch.bool or a.is_floating_point())):
+                raise ValueError(f"{fn}: an alpha is a bool or float tensor of its object's size {tuple(o.shape[:2])}")
+    if pairs is None:
+        plist = [(b, o) for b in range(nb) for o in range(no)]
+    else:
+        plist = [(operator.index(b), operator.index(o)) for b, o in (pairs.tolist() if torch.is_tensor(pairs) else pairs)]
+        if not plist:
+            raise ValueError(f"{fn} needs at least one pair")
+    for b, o in plist:
+        if not (0 <= b < nb and 0 <= o < no):
+            raise ValueError(f"a pair is (background, object) with indices in [0, {nb}) and [0, {no}); got ({b}, {o})")
+    n = len(plist)
+    opacity = float(opacity)
+    if not 0.0 <= opacity <= 1.0:
+        raise ValueError(f"opacity must be in [0, 1]; got {opacity}")
+    if edge not in _EDGES:
+        raise ValueError(f"edge must be 'soft' or 'hard'; got {edge!r}")
+    samples = _check_samples(fn, samples)
+    t_scale, (c_scale,) = _placement_columns(fn, "scale", scale, 1, n)
+    t_rot, (c_rot,) = _placement_columns(fn, "rotation", rotation, 1, n)
+    t_off, c_off = _placement_columns(fn, "offset", offset, 2, n)
+    if size is None:
+        if t_scale or t_rot:
+            raise ValueError(f"{fn}: scale or rotation as tensors are not read back, so the size of the transformed object cannot be derived: pass size=")
+        if not all(np.isfinite(s) and s > 0.0 for s in c_scale) or not all(np.isfinite(r) for r in c_rot):
+            raise ValueError(f"{fn}: without size=, scale must be finite and > 0 and rotation finite; got {c_scale}, {c_rot}")
+        t_size, c_size = False, None
+    else:
+        t_size, c_size = _placement_columns(fn, "size", size, 2, n)
+    params = [c for is_t, cs in ((t_scale, [c_scale]), (t_rot, [c_rot]), (t_off, c_off), (t_size, c_size or [])) if is_t for c in cs]
+    every = bgs + objs + [a for a in alphas if a is not None] + params
+    if not all(t.is_cuda for t in every):
+        raise PfError(f"{fn} runs on the GPU only (no CPU path)")
+    dev = bgs[0].device if bgs[0].device.index is not None else torch.device("cuda", torch.cuda.current_device())
+    if any((t.device if t.device.index is not None else torch.device("cuda", torch.cuda.current_device())) != dev for t in every):
+        raise ValueError(f"{fn}: images, alphas and placement tensors must be on one device")
+    lib = load_library()
+    if c_size is None:
+        c_size = [[], []]
+        for (b, o), s, r in zip(plist, c_scale, c_rot):
+            hw = (ctypes.c_int32 * 2)()
+            if lib.pf_fields_transform_size(int(objs[o].shape[0]), int(objs[o].shape[1]), s, r, hw) != 0:
+                raise ValueError(f"{fn}: {lib.pf_last_error(None).decode()}")
+            c_size[0].append(float(hw[0]))
+            c_size[1].append(float(hw[1]))
+    cols = [c_scale, c_rot, *c_off, *c_size]
+    if any(torch.is_tensor(c) for c in cols):
+        place = torch.stack([c if torch.is_tensor(c) else torch.tensor(c, dtype=torch.float64, device=dev) for c in cols], 1).contiguous()
+    else:
+        place = torch.tensor([list(row) for row in zip(*cols)], dtype=torch.float64, device=dev)
+    bgs, objs = [t.contiguous() for t in bgs], [t.contiguous() for t in objs]
+    alphas = [None if a is None else a.to(torch.float32).contiguous() for a in alphas]
+    same = len({tuple(bgs[b].shape) for b, _ in plist}) == 1
+    if kind_b != "list" and same:
+        stack = torch.empty((n,) + tuple(bgs[0].shape), dtype=bgs[0].dtype, device=dev)
+        outs = list(stack.unbind(0))
+    else:
+        stack, outs = None, [torch.empty_like(bgs[b]) for b, _ in plist]
+    npx = [int(bgs[b].shape[0]) * int(bgs[b].shape[1]) for b, _ in plist]
+    cov = torch.empty(sum(npx), dtype=torch.float32, device=dev) if return_coverage else None
+    ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[None if t is None else t.data_ptr() for t in ts])
+    sizes = lambda ts: (ctypes.c_int32 * (2 * len(ts)))(*[int(s) for t in ts for s in t.shape[:2]])
+    c_jobs = (ctypes.c_int32 * (2 * n))(*[i for bo in plist for i in bo])
+    need = int(lib.pf_composite_workspace_bytes(n))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib.pf_composite(dev.index, nb, ptrs(bgs), sizes(bgs), no, ptrs(objs), ptrs(alphas), sizes(objs), _PANO_DTYPES[bgs[0].dtype], n, c_jobs,
+                                place.data_ptr(), opacity, _EDGES[edge], samples, ptrs(outs), None if cov is None else cov.data_ptr(), ws.data_ptr(), need,
+                                _stream_ptr()), None, "pf_composite")
+    single = kind_b == "single" and kind_o == "single" and n == 1
+    res = outs[0] if single else outs if stack is None else stack
+    if not return_coverage:
+        return res
+    first = np.concatenate([[0], np.cumsum(npx)])
+    covs = [cov[first[k]:first[k + 1]].view(bgs[b].shape[0], bgs[b].shape[1]) for k, (b, _) in enumerate(plist)]
+    return res, (covs[0] if single else covs if stack is None else cov.view(n, *bgs[0].shape[:2]))
 
 
 class FieldErrorAccumulator:
