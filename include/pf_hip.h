@@ -595,6 +595,59 @@ int pf_cube_to_pano(int device, int n_cube, const void* const* h_cube, const int
                     const int32_t* h_cube_index /*[batch]*/, const float* d_rot3 /*[batch][3] roll, pitch, yaw, radians*/, int inverse, int H, int W,
                     void* d_img /*[batch][H][W][3], dtype*/, int samples, void* stream);
 
+/* Fisheye and dual-fisheye frames as a source: camera views and equirectangular panoramas out of one or two lenses of a frame on the device
+ * (fisheye_gather.hip).
+ * THE LENS MODEL.  Conventions are pf_pano_crop's and pf_cube_crop's: x right, y down, z forward, world up (0, -1, 0); R(r, p) = R_pitch R_roll, Y(psi)
+ * the turn about y; pixel-edge image coordinates, a texel centre at integer + 1/2.  A FRAME is (Hs, Ws, 3), uint8 or fp32, channel-interleaved,
+ * Hs, Ws >= 1, and carries up to PF_FISHEYE_MAX_LENSES = 2 LENSES.  A lens is PF_FISHEYE_LENS_FLOATS = 12 fp32 values in this order:
+ *   {roll, pitch, yaw (RADIANS), F, Cx, Cy, theta_max, k1, k2, k3, k4, band}
+ * Q = Y(yaw) R(roll, pitch) is the lens -> world rotation; F is in pixels per unit of rho; (Cx, Cy) is the centre of the image circle in pixel-edge
+ * units of the frame; theta_max is the half field of view in radians, up to pi; band >= 0 is the feather width in radians.  The projection kind is
+ * one integer per call: PF_FISHEYE_EQUIDISTANT rho(t) = t, PF_FISHEYE_EQUISOLID rho(t) = 2 sin(t / 2), PF_FISHEYE_STEREOGRAPHIC rho(t) = 2 tan(t / 2);
+ * k1 ... k4 are the Kannala-Brandt polynomial (OpenCV's fisheye model is the equidistant kind with F = f).  Only the forward projection
+ * (direction -> pixel) is used, so nothing is inverted on the device.
+ * The value of a frame in a unit world direction D, per lens l = 0, 1 in that order:
+ *   1 angle     X = Ql^T D, h = hypot(X.x, X.y), theta = atan2(h, X.z)
+ *   2 point     theta_d = theta (1 + theta^2 (k1 + theta^2 (k2 + theta^2 (k3 + theta^2 k4)))), Horner-wise as written; r = F rho(theta_d);
+ *               (a, b) = (Cx, Cy) + r (X.x, X.y) / h, and (Cx, Cy) itself where h = 0
+ *   3 covered   iff theta_max - theta > 0 and 0 <= a <= Ws and 0 <= b <= Hs.  Every comparison is a positive one: a lens with a non-finite entry or
+ *               with theta_max <= 0 covers nothing and issues no load, which is also how an unused second lens is switched off
+ *   4 weight    w = min((theta_max - theta) / band, 1) for band > 0, else 1
+ *   5 colour    c = the bilinear sample of the other gathers at (a - 1/2, b - 1/2), taps clamped into the frame
+ * Then S = sum of w and C = sum of w c, in fp32, in lens order; the direction is VALID iff S > 0 and its value is C / S.  For a dual-fisheye camera
+ * `band` is the overlap of the two lenses (fov - 180 degrees): one lens fades out exactly where the other fades in.
+ * pf_fisheye_crop: views of cameras theta = d_cam7 row = {roll, pitch, yaw (RADIANS), rel_focal, rel_cx, rel_cy, xi}: the ray of pf_pano_crop's pixel
+ * (pinhole or Unified Spherical Model), D = Y(yaw) R(roll, pitch) ray as in pf_cube_crop, the frame's value in D.  A pixel without a ray or
+ * without a covering lens is `fill`, and its mask is 0.
+ * pf_fisheye_to_pano: equirectangular panoramas; pixel -> direction D0 and the rotation A = Q or Q^T of pf_pano_rotate (d_rot3, inverse), D = A D0,
+ * the frame's value in D: a tilted rig is levelled into a panorama in one pass.
+ * Both: `samples` = S in 1 ... PF_GATHER_MAX_SAMPLES under the rule of the supersampled gathers above: every pixel is the mean of the valid ones of
+ * the S x S sub-samples at (col + (j + 1/2)/S, row + (i + 1/2)/S), each the blended value above: the fp32 sum i-major then j divided by their
+ * count; `fill` without one; the mask is 1 iff a sub-sample is valid.  PF_PANO_U8: the fp32 value rounded half up, clamped to [0, 255].  A non-finite
+ * camera or angle entry: the output is `fill`, its mask 0, and no load is issued for it.  There are no labels: the fields of a view or of a
+ * panoramic camera do not depend on the source (pf_fields_from_params, pf_pano_fields).
+ * h_frame = HOST array of n_frame DEVICE pointers to (Hs, Ws, 3) of type `dtype`; h_frame_hw = HOST [n_frame][2] (Hs, Ws); h_frame_index = HOST
+ * [batch], the frame of each output; d_lens = DEVICE [batch][2][12], the two lenses of each output (of its frame); d_img = DEVICE
+ * [batch][H][W][3] of `dtype`; d_valid = NULL or DEVICE [batch][H][W] bytes.  The 4-pixel vector stores are taken when W % 4 == 0 and d_img
+ * (4 bytes uint8, 16 bytes fp32) and d_valid (4 bytes) are aligned; otherwise scalar stores give the same bits.  Argument errors return PF_ERR_ARG
+ * before any device work with a message that begins with the function's name, checked in this order: `samples` out of range; an unknown `kind`;
+ * then n_frame < 1 or NULL source lists, a bad dtype, a NULL frame or a frame side < 1, batch < 1 or a NULL required pointer (h_frame_index,
+ * d_lens, d_cam7 / d_rot3, d_img), H or W < 1, an index out of range.  One launch per 32 outputs on `stream`, no workspace, no host
+ * synchronisation; stateless, no handle; deterministic, each output's bits independent of the batch it is in. */
+#define PF_FISHEYE_MAX_LENSES 2
+#define PF_FISHEYE_LENS_FLOATS 12
+#define PF_FISHEYE_EQUIDISTANT 0
+#define PF_FISHEYE_EQUISOLID 1
+#define PF_FISHEYE_STEREOGRAPHIC 2
+int pf_fisheye_crop(int device, int n_frame, const void* const* h_frame, const int32_t* h_frame_hw /*[n_frame][2]*/, int dtype /*PF_PANO_U8|PF_PANO_F32*/,
+                    int kind /*PF_FISHEYE_...*/, int batch, const int32_t* h_frame_index /*[batch]*/, const float* d_lens /*[batch][2][12]*/,
+                    const float* d_cam7 /*[batch][7]*/, int H, int W, float fill, void* d_img /*[batch][H][W][3], dtype*/, uint8_t* d_valid /*or NULL*/,
+                    int samples, void* stream);
+int pf_fisheye_to_pano(int device, int n_frame, const void* const* h_frame, const int32_t* h_frame_hw /*[n_frame][2]*/, int dtype, int kind, int batch,
+                       const int32_t* h_frame_index /*[batch]*/, const float* d_lens /*[batch][2][12]*/,
+                       const float* d_rot3 /*[batch][3] roll, pitch, yaw, radians*/, int inverse, int H, int W, float fill,
+                       void* d_img /*[batch][H][W][3], dtype*/, uint8_t* d_valid /*or NULL*/, int samples, void* stream);
+
 /* The relative yaw of camera views of one centre, from the pictures: for ordered pairs (a, b) of views and a list of candidate turns, the moments of
  * the two luminance images on their overlap, from which the zero-mean normalised cross-correlation follows (yaw_align.hip).
  * The fields give roll, pitch and intrinsics of a view but not the direction it faces; with those known, two views of one centre differ by a single

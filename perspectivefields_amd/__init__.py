@@ -9,7 +9,7 @@ Sub-modules: config (zoo / cfg), schema (checkpoint keys), synth (seeded checkpo
 engine (ctypes binding of libpf_hip.so), ops (kernel-level entry points), dist (image-level data
 parallelism), build (hipcc build of csrc/).
 """
-__all__ = ["PerspectiveFields", "model_zoo", "fields_from_params", "fit_camera_params", "fit_camera_shared", "crop_panorama", "reproject_image", "compose_panorama", "rotate_panorama", "panorama_fields", "gravity_from_views", "crop_cubemap", "cubemap_to_panorama", "panorama_to_cubemap", "cubemap_face_cameras", "cubemap_to_image", "cubemap_from_image", "yaw_scores", "align_yaw", "yaw_tree", "placement_scores", "placement_search", "transform_fields", "composite_objects", "draw_perspective_fields", "draw_camera", "field_errors", "FieldErrorAccumulator"]
+__all__ = ["PerspectiveFields", "model_zoo", "fields_from_params", "fit_camera_params", "fit_camera_shared", "crop_panorama", "reproject_image", "compose_panorama", "rotate_panorama", "panorama_fields", "gravity_from_views", "crop_cubemap", "cubemap_to_panorama", "panorama_to_cubemap", "cubemap_face_cameras", "cubemap_to_image", "cubemap_from_image", "fisheye_lens", "dual_fisheye_lenses", "crop_fisheye", "fisheye_to_panorama", "yaw_scores", "align_yaw", "yaw_tree", "placement_scores", "placement_search", "transform_fields", "composite_objects", "draw_perspective_fields", "draw_camera", "field_errors", "FieldErrorAccumulator"]
 
 
 def __getattr__(name):  # lazy: keeps `import perspectivefields_amd.synth` free of torch
@@ -46,6 +46,10 @@ def __getattr__(name):  # lazy: keeps `import perspectivefields_amd.synth` free 
 
         return getattr(_pfm, name)
     if name in ("crop_cubemap", "cubemap_to_panorama", "panorama_to_cubemap", "cubemap_face_cameras", "cubemap_to_image", "cubemap_from_image"):
+        from . import perspectivefields as _pfm
+
+        return getattr(_pfm, name)
+    if name in ("fisheye_lens", "dual_fisheye_lenses", "crop_fisheye", "fisheye_to_panorama"):
         from . import perspectivefields as _pfm
 
         return getattr(_pfm, name)

@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the pasting of objects (composite.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip, fisheye_gather.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the pasting of objects (composite.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include "host_pack.h"
 
 using namespace pf;
@@ -205,6 +205,49 @@ int pf_cube_to_pano(int device, int n_cube, const void* const* cube, const int32
                       cb.samples = samples;
                       cb.inverse = inverse ? 1 : 0;
                       cb.rot = d_rot3 + (size_t)i0 * 3;
+                    });
+}
+
+// Fisheye frames as the source (fisheye_gather.hip): `samples`, then the projection kind, then gather_run's checks; the lenses are a required argument
+static bool fisheye_kind_ok(const char* name, int kind) {
+  if (kind == PF_FISHEYE_EQUIDISTANT || kind == PF_FISHEYE_EQUISOLID || kind == PF_FISHEYE_STEREOGRAPHIC) return true;
+  g_create_error = fmt("%s: unknown projection kind %d", name, kind);
+  return false;
+}
+
+int pf_fisheye_crop(int device, int n_frame, const void* const* frame, const int32_t* frame_hw, int dtype, int kind, int B, const int32_t* frame_index,
+                    const float* d_lens, const float* d_cam7, int H, int W, float fill, void* d_img, uint8_t* d_valid, int samples, void* stream) {
+  static const GatherKind gk{"pf_fisheye_crop", "frame", "view", 1, "needs at least one frame (h_frame, h_frame_hw)",
+                             "batch >= 1, h_frame_index, d_lens, d_cam7 and d_img are required"};
+  if (!samples_ok(gk.name, samples) || !fisheye_kind_ok(gk.name, kind)) return PF_ERR_ARG;
+  const size_t npx = (size_t)H * W;
+  return gather_run(gk, launch_fisheye_crop, device, n_frame, frame, frame_hw, dtype, B, frame_index, d_lens && d_cam7, H, W, d_img, nullptr,
+                    misalign(d_valid, 3), stream, [=](FisheyeCropBatch& fb, int i0) {
+                      fb.samples = samples;
+                      fb.kind = kind;
+                      fb.fill = fill;
+                      fb.lens = d_lens + (size_t)i0 * PF_FISHEYE_MAX_LENSES * PF_FISHEYE_LENS_FLOATS;
+                      fb.cam = d_cam7 + (size_t)i0 * 7;
+                      fb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
+                    });
+}
+
+int pf_fisheye_to_pano(int device, int n_frame, const void* const* frame, const int32_t* frame_hw, int dtype, int kind, int B, const int32_t* frame_index,
+                       const float* d_lens, const float* d_rot3, int inverse, int H, int W, float fill, void* d_img, uint8_t* d_valid, int samples,
+                       void* stream) {
+  static const GatherKind gk{"pf_fisheye_to_pano", "frame", "output", 1, "needs at least one frame (h_frame, h_frame_hw)",
+                             "batch >= 1, h_frame_index, d_lens, d_rot3 and d_img are required"};
+  if (!samples_ok(gk.name, samples) || !fisheye_kind_ok(gk.name, kind)) return PF_ERR_ARG;
+  const size_t npx = (size_t)H * W;
+  return gather_run(gk, launch_fisheye_to_pano, device, n_frame, frame, frame_hw, dtype, B, frame_index, d_lens && d_rot3, H, W, d_img, nullptr,
+                    misalign(d_valid, 3), stream, [=](FisheyePanoBatch& fb, int i0) {
+                      fb.samples = samples;
+                      fb.kind = kind;
+                      fb.fill = fill;
+                      fb.inverse = inverse ? 1 : 0;
+                      fb.lens = d_lens + (size_t)i0 * PF_FISHEYE_MAX_LENSES * PF_FISHEYE_LENS_FLOATS;
+                      fb.rot = d_rot3 + (size_t)i0 * 3;
+                      fb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
                     });
 }
 

@@ -575,6 +575,39 @@ void launch_cube_to_pano(const CubePanoBatch& cb, int dtype, hipStream_t s);
 static_assert(offsetof(CubeCropBatch, samples) == 28 && offsetof(CubeCropBatch, src) == 32, "CubeCropBatch layout");
 static_assert(offsetof(CubePanoBatch, samples) == 28 && offsetof(CubePanoBatch, src) == 32, "CubePanoBatch layout");
 
+// fisheye and dual-fisheye frames -> camera views and equirectangular panoramas (fisheye_gather.hip, include/pf_hip.h pf_fisheye_crop /
+// pf_fisheye_to_pano): the sources are frames (Hs, Ws, 3), each output reads up to PF_FISHEYE_MAX_LENSES lenses of its one frame; `samples` as in
+// the supersampled gathers
+struct FisheyeCropBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int samples;        // S in [1, PF_GATHER_MAX_SAMPLES]
+  GatherSources src;  // the frames
+  int kind;           // PF_FISHEYE_EQUIDISTANT | PF_FISHEYE_EQUISOLID | PF_FISHEYE_STEREOGRAPHIC
+  float fill;         // value of a pixel that no lens covers
+  const float* lens;  // [n][PF_FISHEYE_MAX_LENSES][PF_FISHEYE_LENS_FLOATS]
+  const float* cam;   // [n][7], as PanoBatch
+  void* img;          // [n][H][W][3], the frames' type
+  uint8_t* valid;     // NULL or [n][H][W]: 1 where a sub-sample is covered
+};
+void launch_fisheye_crop(const FisheyeCropBatch& fb, int dtype, hipStream_t s);
+struct FisheyePanoBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int samples;
+  GatherSources src;  // the frames
+  int kind;
+  float fill;
+  int inverse;        // as PanoRotBatch
+  const float* lens;  // [n][PF_FISHEYE_MAX_LENSES][PF_FISHEYE_LENS_FLOATS]
+  const float* rot;   // [n][3]: roll, pitch, yaw (radians)
+  void* img;
+  uint8_t* valid;
+};
+void launch_fisheye_to_pano(const FisheyePanoBatch& fb, int dtype, hipStream_t s);
+static_assert(offsetof(FisheyeCropBatch, samples) == 28 && offsetof(FisheyeCropBatch, src) == 32, "FisheyeCropBatch layout");
+static_assert(offsetof(FisheyePanoBatch, samples) == 28 && offsetof(FisheyePanoBatch, src) == 32, "FisheyePanoBatch layout");
+
 // camera views of one centre -> equirectangular panoramas (pano_compose.hip, include/pf_hip.h pf_pano_compose): the outputs of a launch are up to MAX
 // panoramas, its sources up to MAX views; panorama k blends the views [first[k], first[k] + count[k]) of the launch in that order
 struct ComposeBatch {

@@ -2062,6 +2062,227 @@ def cubemap_to_panorama(cube, *, height, width, roll=0.0, pitch=0.0, yaw=0.0, in
     return img, up, lat
 
 
+# projection kinds and lens layout of the fisheye gathers (include/pf_hip.h PF_FISHEYE_*)
+FISHEYE_PROJECTIONS = {"equidistant": 0, "equisolid": 1, "stereographic": 2}
+FISHEYE_MAX_LENSES, FISHEYE_LENS_FLOATS = 2, 12
+_FISHEYE_RHO = {"equidistant": lambda t: t, "equisolid": lambda t: 2.0 * np.sin(0.5 * t), "stereographic": lambda t: 2.0 * np.tan(0.5 * t)}
+
+
+def _fisheye_kind(fn, projection):
+    if projection not in FISHEYE_PROJECTIONS:
+        raise ValueError(f"{fn}: projection must be one of {sorted(FISHEYE_PROJECTIONS)}; got {projection!r}")
+    return FISHEYE_PROJECTIONS[projection]
+
+
+def fisheye_lens(fov, *, radius, center, projection="equidistant", k=(0.0, 0.0, 0.0, 0.0), roll=0.0, pitch=0.0, yaw=0.0, band=0.0, mode="deg"):
+    """One lens row of the fisheye gathers (include/pf_hip.h, the lens model): 12 float64 values {roll, pitch, yaw (radians), F, Cx, Cy, theta_max,
+    k1, k2, k3, k4, band}, from what a user knows about the lens.
+
+    fov: the full field of view, in (0, 360] degrees; `radius`: the radius in pixels of the image circle, where the ray at fov / 2 lands;
+    center = (Cx, Cy): the circle's centre in pixel-edge units of the frame (a texel centre is at integer + 1/2); projection: "equidistant"
+    (rho = theta), "equisolid" (2 sin(theta / 2)) or "stereographic" (2 tan(theta / 2)); k = (k1, k2, k3, k4): the Kannala-Brandt polynomial
+    theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8), OpenCV's fisheye model with the equidistant kind; roll, pitch, yaw: the
+    lens -> world rotation Y(yaw) R(roll, pitch) in the conventions of `crop_panorama`; band: the feather width, the angle before fov / 2 over
+    which the lens fades out.  fov, band and the angles are degrees unless mode="rad".  F = radius / rho(theta_d(fov / 2)).
+    r(theta) = rho(theta_d(theta)) is evaluated in fp64 on [0, fov / 2]; a ValueError is raised if it is not strictly increasing: the polynomial is
+    then not a lens."""
+    fn = "fisheye_lens"
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    _fisheye_kind(fn, projection)
+    conv = np.radians if mode == "deg" else (lambda a: a)
+    vals = [float(v) for v in (fov, radius, band, roll, pitch, yaw)]
+    cx, cy = (float(c) for c in center)
+    ks = [float(v) for v in k]
+    if len(ks) != 4:
+        raise ValueError(f"{fn}: k has 4 coefficients (k1, k2, k3, k4); got {len(ks)}")
+    if not np.isfinite(vals + [cx, cy] + ks).all():
+        raise ValueError(f"{fn}: every value must be finite")
+    tmax, band_r = 0.5 * float(conv(vals[0])), float(conv(vals[2]))
+    if not 0.0 < tmax <= np.pi:
+        raise ValueError(f"{fn}: fov must be in (0, {'360] degrees' if mode == 'deg' else '2 pi] radians'}; got {fov!r}")
+    if not vals[1] > 0.0:
+        raise ValueError(f"{fn}: radius must be > 0; got {radius!r}")
+    if band_r < 0.0:
+        raise ValueError(f"{fn}: band must be >= 0; got {band!r}")
+    t = np.linspace(0.0, tmax, 4097)
+    t2 = t * t
+    td = t * (1.0 + t2 * (ks[0] + t2 * (ks[1] + t2 * (ks[2] + t2 * ks[3]))))
+    with np.errstate(all="ignore"):
+        r = _FISHEYE_RHO[projection](td)
+    if not (np.isfinite(r).all() and (np.diff(r) > 0.0).all()):
+        raise ValueError(f"{fn}: r(theta) is not strictly increasing on [0, fov / 2]: projection {projection!r} with k = {tuple(ks)} is not a lens")
+    return np.array([conv(vals[3]), conv(vals[4]), conv(vals[5]), vals[1] / r[-1], cx, cy, tmax, *ks, band_r], dtype=np.float64)
+
+
+def dual_fisheye_lenses(height, width, fov, **kw):
+    """The two lens rows (2, 12) of the usual side-by-side dual-fisheye frame (height, width) of a two-lens 360 degree camera: image circles centred
+    at (width / 4, height / 2) and (3 width / 4, height / 2) with radius min(width / 4, height / 2), the second lens at yaw + 180 degrees, and
+    band = fov - 180 degrees, the overlap of the two lenses, so that one lens fades out exactly where the other fades in.  fov and the keywords
+    projection, k, roll, pitch, yaw, mode (and band, to override the default) are `fisheye_lens`'s."""
+    fn = "dual_fisheye_lenses"
+    H, W = float(height), float(width)
+    if not (H >= 1 and W >= 2):
+        raise ValueError(f"{fn}: the frame must be at least 1 x 2; got {height} x {width}")
+    if "radius" in kw or "center" in kw:
+        raise TypeError(f"{fn}: radius and center follow from the frame")
+    mode = kw.get("mode", "deg")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    half = 180.0 if mode == "deg" else np.pi
+    band = kw.pop("band", max(float(fov) - half, 0.0))
+    yaw = float(kw.pop("yaw", 0.0))
+    radius = min(W / 4.0, H / 2.0)
+    return np.stack([fisheye_lens(fov, radius=radius, center=(W / 4.0, H / 2.0), yaw=yaw, band=band, **kw),
+                     fisheye_lens(fov, radius=radius, center=(3.0 * W / 4.0, H / 2.0), yaw=yaw + half, band=band, **kw)])
+
+
+def _fisheye_frames(fn, frames):
+    """the frames of a fisheye gather: (Hs, Ws, 3) CUDA tensors of one dtype and one device -> (list, device)"""
+    return _cuda_image_list(fn, [frames] if torch.is_tensor(frames) else list(frames), ("frame", "frames"), "a frame must be (Hs, Ws, 3) with Hs, Ws >= 1", 1)
+
+
+def _fisheye_lens_table(fn, lenses, n_frame):
+    """`lenses` -> (n_frame, 2, 12) float64.  Anything 1-d or 2-d is ONE entry shared by every frame: a row (12,), or 1 or 2 rows ((1, 12), (2, 12),
+    also as a list of two rows, so two rows are always the two lenses of a frame, never one lens each for two frames).  Per frame: an array
+    (n_frame, 1 or 2, 12), or a list of n_frame 2-d entries ((1, 12) for a frame with one lens).  A missing second lens is a row of zeros:
+    theta_max = 0 switches it off"""
+    def host(e):
+        return e.detach().cpu().numpy() if torch.is_tensor(e) else e
+
+    def entry(e):
+        a = np.asarray(host(e), dtype=np.float64)
+        if a.ndim == 1:
+            a = a[None]
+        if a.ndim != 2 or a.shape[1] != FISHEYE_LENS_FLOATS or not 1 <= a.shape[0] <= FISHEYE_MAX_LENSES:
+            raise ValueError(f"{fn}: a frame's lenses are one row of {FISHEYE_LENS_FLOATS} values or {FISHEYE_MAX_LENSES} such rows; got shape {tuple(a.shape)}")
+        return np.concatenate([a, np.zeros((FISHEYE_MAX_LENSES - a.shape[0], FISHEYE_LENS_FLOATS))])
+
+    ndim = lambda e: e.dim() if torch.is_tensor(e) else np.ndim(e)
+    if isinstance(lenses, (list, tuple)):
+        per_frame = len(lenses) > 0 and all(ndim(e) == 2 for e in lenses)
+    else:
+        per_frame = ndim(lenses) == 3
+    if not per_frame:
+        return np.repeat(entry(lenses)[None], n_frame, axis=0)
+    if len(lenses) != n_frame:
+        raise ValueError(f"{fn}: lenses has {len(lenses)} entries for {n_frame} frames")
+    return np.stack([entry(e) for e in lenses])
+
+
+def _frame_index(frame_index, B, n, what):
+    if frame_index is None:
+        return [0] * B
+    idx = [operator.index(i) for i in (frame_index.tolist() if torch.is_tensor(frame_index) else frame_index)]
+    if len(idx) != B:
+        raise ValueError(f"frame_index has {len(idx)} entries for {B} {what}")
+    if any(i < 0 or i >= n for i in idx):
+        raise ValueError(f"frame_index entries must be in [0, {n})")
+    return idx
+
+
+def crop_fisheye(frames, lenses, roll, pitch, rel_focal, rel_cx=0.0, rel_cy=0.0, *, yaw=0.0, xi=0.0, height, width, frame_index=None, projection="equidistant",
+                 mode="deg", fields=True, samples=1, fill=0, return_mask=False):
+    """Fisheye and dual-fisheye frames -> camera views and their ground-truth perspective fields on the GPU: `crop_panorama` for the raw frames of a
+    fisheye lens or of a two-lens 360 degree camera, without stitching a panorama first; with xi = 0 the view is the undistorted picture.  Lens
+    model and sampling: include/pf_hip.h pf_fisheye_crop.
+
+    frames: a CUDA tensor (Hs, Ws, 3), uint8 or float32, or a list of them (one dtype, one device; sizes may differ).  lenses: a row of
+    `fisheye_lens`, a pair of rows (`dual_fisheye_lenses`; two lenses are blended across their overlap), both shared by every frame, or one such
+    entry per frame (a list of (1 or 2, 12) arrays, or an array (n_frames, 1 or 2, 12)); two plain rows are always the two lenses of one frame,
+    so two frames with one lens each take two (1, 12) entries.  The rows hold radians and are read on the host.
+    projection: the kind of every lens of the call.  The camera parameters, mode, height, width and samples are `crop_panorama`'s; frame_index:
+    None (every view from frame 0) or B integers.  fill: the value of the pixels without a ray or without a covering lens.
+    Returns (images (B, H, W, 3) in the frames' dtype, up (B, 2, H, W), lat (B, H, W) degrees), and the mask (B, H, W) bool as a fourth entry with
+    return_mask=True; up / lat are `fields_from_params` of the same parameters (they do not depend on the source) and None with fields=False.  A
+    view with a non-finite parameter is `fill`.  GPU only: CPU frames raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    fn = "crop_fisheye"
+    samples = _check_samples(fn, samples)
+    kind = _fisheye_kind(fn, projection)
+    srcs, dev = _fisheye_frames(fn, frames)
+    H, W = int(height), int(width)
+    if H < 1 or W < 1:
+        raise ValueError(f"view size must be at least 1 x 1; got {H} x {W}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    fill = float(fill)
+    ts = _rotation_params(fn, (("roll", roll), ("pitch", pitch), ("yaw", yaw), ("rel_focal", rel_focal), ("rel_cx", rel_cx), ("rel_cy", rel_cy), ("xi", xi)))
+    B = _broadcast_len(fn, ts)
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one view")
+    idx = _frame_index(frame_index, B, len(srcs), "views")
+    table = _fisheye_lens_table(fn, lenses, len(srcs))
+    cam = _camera_rows(ts, (0, 1, 2), B, dev, mode).contiguous()
+    lens = torch.from_numpy(np.ascontiguousarray(table[idx], dtype=np.float32)).to(dev)
+    srcs = [p.contiguous() for p in srcs]
+    img = torch.empty((B, H, W, 3), dtype=srcs[0].dtype, device=dev)
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_mask else None
+    p_src, hw, c_idx = _source_arrays(srcs, [(int(p.shape[0]), int(p.shape[1])) for p in srcs], idx)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_fisheye_crop(dev.index, len(srcs), p_src, hw, _PANO_DTYPES[srcs[0].dtype], kind, B, c_idx, lens.data_ptr(), cam.data_ptr(), H, W, fill,
+                                   img.data_ptr(), valid.data_ptr() if return_mask else None, samples, _stream_ptr()), None, "pf_fisheye_crop")
+    mask = (valid.view(torch.bool),) if return_mask else ()
+    if not fields:
+        return (img, None, None) + mask
+    pinhole = not torch.is_tensor(xi) and np.ndim(xi) == 0 and float(xi) == 0.0   # fields_from_params' rule: the number 0 is the pinhole model
+    rows = [t.expand(B) for t in ts]
+    per_view = [fields_from_params(rows[0][i], rows[1][i], rows[3][i], rows[4][i], rows[5][i], height=H, width=W, mode=mode, device=dev,
+                                   xi=0.0 if pinhole else rows[6][i]) for i in range(B)]
+    return (img, torch.stack([u for u, _ in per_view]), torch.stack([l for _, l in per_view])) + mask
+
+
+def fisheye_to_panorama(frames, lenses, *, height, width, roll=0.0, pitch=0.0, yaw=0.0, inverse=False, frame_index=None, projection="equidistant", mode="deg",
+                        fields=False, samples=1, fill=0, return_mask=False):
+    """Fisheye and dual-fisheye frames -> equirectangular panoramas on the GPU, turned on the way if angles are given: the two lenses of a 360
+    degree camera are blended across their overlap, and a tilted rig is levelled into a panorama in one pass.  Lens model and sampling:
+    include/pf_hip.h pf_fisheye_to_pano.
+
+    frames, lenses, projection, frame_index, fill: as `crop_fisheye`.  roll, pitch, yaw, inverse, mode, samples: `rotate_panorama`'s, with the
+    frame in the place of the source panorama (inverse=False: what a panoramic camera with that orientation among the lenses sees;
+    inverse=True: a frame shot by a rig with that orientation becomes upright).  height, width: the size of every output.
+    Returns the images (B, H, W, 3) in the frames' dtype; with fields=True (images, up, lat), the fields being `panorama_fields(roll, pitch)`;
+    with return_mask=True the mask (B, H, W) bool comes last: False where no lens covers the pixel, which then holds `fill`.  Non-finite angles
+    give an image of `fill`.  GPU only: CPU frames raise PfError."""
+    from .engine import _check, _stream_ptr, load_library
+
+    fn = "fisheye_to_panorama"
+    samples = _check_samples(fn, samples)
+    kind = _fisheye_kind(fn, projection)
+    srcs, dev = _fisheye_frames(fn, frames)
+    H, W = int(height), int(width)
+    if H < 1 or W < 1:
+        raise ValueError(f"output size must be at least 1 x 1; got {H} x {W}")
+    if mode not in ("deg", "rad"):
+        raise ValueError("mode must be 'deg' or 'rad'")
+    fill = float(fill)
+    ts = _rotation_params(fn, (("roll", roll), ("pitch", pitch), ("yaw", yaw)))
+    B = _broadcast_len(fn, ts)
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one output")
+    idx = _frame_index(frame_index, B, len(srcs), "outputs")
+    table = _fisheye_lens_table(fn, lenses, len(srcs))
+    rot = _camera_rows(ts, (0, 1, 2), B, dev, mode).contiguous()
+    lens = torch.from_numpy(np.ascontiguousarray(table[idx], dtype=np.float32)).to(dev)
+    srcs = [p.contiguous() for p in srcs]
+    img = torch.empty((B, H, W, 3), dtype=srcs[0].dtype, device=dev)
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_mask else None
+    p_src, hw, c_idx = _source_arrays(srcs, [(int(p.shape[0]), int(p.shape[1])) for p in srcs], idx)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        _check(lib.pf_fisheye_to_pano(dev.index, len(srcs), p_src, hw, _PANO_DTYPES[srcs[0].dtype], kind, B, c_idx, lens.data_ptr(), rot.data_ptr(),
+                                      1 if inverse else 0, H, W, fill, img.data_ptr(), valid.data_ptr() if return_mask else None, samples, _stream_ptr()),
+               None, "pf_fisheye_to_pano")
+    out = (img,)
+    if fields:
+        out += tuple(panorama_fields(ts[0].expand(B), ts[1].expand(B), height=H, width=W, mode=mode, device=dev))
+    if return_mask:
+        out += (valid.view(torch.bool),)
+    return out[0] if len(out) == 1 else out
+
+
 def panorama_to_cubemap(pano, size, *, roll=0.0, pitch=0.0, yaw=0.0, samples=1):
     """Equirectangular panoramas -> cube maps on the GPU: the six `crop_panorama` views of `cubemap_face_cameras()` at size x size, bit for bit.
     pano: a CUDA tensor (Hp, Wp, 3), uint8 or float32, or a list of B of them.  roll, pitch, yaw (degrees; numbers or B values): when one is given the
