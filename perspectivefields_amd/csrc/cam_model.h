@@ -107,6 +107,70 @@ __device__ __forceinline__ void to_world(const float* R, const float* X, float* 
   Xw[2] = R[6] * X[0] + R[7] * X[1] + R[8] * X[2];
 }
 
+// ---------------------------------------------------------------- Model pieces of the supersampled gathers (gather_ss.h), each written once.  Every
+// rounding step is spelled out (contraction off, fmaf where a fused step is meant): the bits must not depend on the kernel they are inlined into.
+// pano_rotate.hip calls pano_rotation (its kernels compile to the same instructions with it) and keeps its own pixel ->
+// direction inside its rot_pixel, which has no sub-sample offset.
+__device__ __forceinline__ bool all_finite(const float* p, int n) {
+  bool fin = true;
+  for (int k = 0; k < n; ++k) fin = fin && isfinite(p[k]);
+  return fin;
+}
+
+// Q = Y(yaw) R_pitch(pitch) R_roll(roll), camera -> world, row major; Y = [[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]
+__device__ __forceinline__ void world_rotation(float roll, float pitch, float yaw, float* Q) {
+#pragma clang fp contract(off)
+  float R[9], sy, cy;
+  cam_rotation(roll, pitch, R);
+  sincosf(yaw, &sy, &cy);
+  for (int k = 0; k < 3; ++k) {
+    Q[k] = fmaf(cy, R[k], sy * R[6 + k]);
+    Q[3 + k] = R[3 + k];
+    Q[6 + k] = fmaf(cy, R[6 + k], -(sy * R[k]));
+  }
+}
+// A = Q of rot = {roll, pitch, yaw}, or Q^T with `inverse`: output direction -> world direction of a rotated panorama
+__device__ __forceinline__ void pano_rotation(const float* rot, int inverse, float* A) {
+  float Q[9];
+  world_rotation(rot[0], rot[1], rot[2], Q);
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) A[3 * i + j] = inverse ? Q[3 * j + i] : Q[3 * i + j];
+}
+
+// X = A v for a row-major 3 x 3 matrix
+__device__ __forceinline__ void rotate_exact(const float* A, float v0, float v1, float v2, float* X) {
+#pragma clang fp contract(off)
+  X[0] = fmaf(A[2], v2, fmaf(A[1], v1, A[0] * v0));
+  X[1] = fmaf(A[5], v2, fmaf(A[4], v1, A[3] * v0));
+  X[2] = fmaf(A[8], v2, fmaf(A[7], v1, A[6] * v0));
+}
+
+// pf_pano_crop's ray C = (eta x, eta y, eta - xi) of the image point (x, y), k1 = 1 - xi^2: rho^2, disc, eta.  False where the point has no ray
+__device__ __forceinline__ bool usm_ray_exact(float x, float y, float xi, float k1, float* C) {
+#pragma clang fp contract(off)
+  const float r2 = fmaf(x, x, y * y);
+  const float disc = fmaf(k1, r2, 1.f);
+  if (!(disc >= 0.f)) return false;
+  const float eta = (xi + sqrtf(disc)) / (1.f + r2);
+  C[0] = eta * x; C[1] = eta * y; C[2] = eta - xi;
+  return true;
+}
+
+// pf_pano_rotate's pixel -> direction.  Sine and cosine of the latitude of the point `off` below the top of row `row` of H rows
+struct PanoRow { float sl, cl; };
+__device__ __forceinline__ PanoRow pano_row(int row, float off, int H) {
+#pragma clang fp contract(off)
+  PanoRow r;
+  sincosf((0.5f - ((float)row + off) / (float)H) * 3.14159265358979323846f, &r.sl, &r.cl);
+  return r;
+}
+// D = (cl so, -sl, cl co) of the point `off` right of the left side of column `col` of W, (so, co) the sine and cosine of its longitude
+__device__ __forceinline__ void pano_direction(const PanoRow& r, int col, float off, int W, float* D, float* so, float* co) {
+#pragma clang fp contract(off)
+  sincosf((((float)col + off) / (float)W - 0.5f) * (2.f * 3.14159265358979323846f), so, co);
+  D[0] = r.cl * *so; D[1] = -r.sl; D[2] = r.cl * *co;
+}
+
 // up vector at a pixel centre whose ray is X
 __device__ __forceinline__ void usm_up_of_ray(const float* X, const float* g, float xi, float* ux, float* uy) {
   const float D = X[2] + xi;

@@ -3,9 +3,8 @@
 //   cube_crop_kernel<T>     views of cameras (roll, pitch, yaw, rel_focal, rel_cx, rel_cy, xi): pf_pano_crop's ray, turned into the world by
 //                           Q = Y(yaw) R_pitch R_roll, sampled in the cube
 //   cube_to_pano_kernel<T>  panoramas: pf_pano_rotate's pixel -> direction X = A D, sampled in the cube
-//       both: grid (tiles per output) x (outputs of the group), 256 threads, a 64 x 16 pixel tile, 4 adjacent pixels of a row per thread, lane 0
-//       computes the output's constants into LDS once per block, 64-bit offsets, vector stores with GatherDims::vec.  `samples` = S is a run-time loop
-//       as in gather_ss.hip: the fp32 sum of the valid sub-samples at offsets (i + 1/2) / S, i-major then j, from -0, divided by their count.
+//       both are models of gather_ss.h, which owns the launch shape, the `samples` loop, the mean and the stores; the ray, the rotation and the
+//       pixel -> direction are cam_model.h's.
 // The sampler (the contract; tests/test_cubemap_ref.py states it in fp64).  A cube is (6, N, N, 3); face k has the frame (r, d, n) of kFace:
 //   face    |z| >= |x| and |z| >= |y|: front (z >= 0) or back; else |x| >= |y|: right (x > 0) or left; else up (y < 0) or down
 //   point   a = (X . r) / (X . n), b = (X . d) / (X . n); u = fma(a, N / 2, N / 2 - 1/2), v likewise: in [-1/2, N - 1/2], texel centres at integers
@@ -21,13 +20,16 @@
 
 #include "../../include/pf_hip.h"
 #include "cam_model.h"
-#include "gather.h"
+#include "gather_ss.h"
+
+// every rounding step of this unit's setup and per-sample functions is spelled out: no contraction in what follows, fmaf where a fused step is meant
+#pragma clang fp contract(off)
 
 namespace pf {
 
 namespace {
 
-constexpr float kPi = 3.14159265358979323846f, kThird = 1.f / 3.f;
+constexpr float kThird = 1.f / 3.f;
 
 // the face frames: right r, down d, forward n of face k = front, right, back, left, up, down (include/pf_hip.h)
 struct Frame { int r[3], d[3], n[3]; };
@@ -88,7 +90,6 @@ __device__ __forceinline__ void tap_or_ring(const T* __restrict__ cube, int N, i
 // any tap of face k, indices in [-1, N]
 template <typename T>
 __device__ __forceinline__ void tap_any(const T* __restrict__ cube, int N, int k, int row, int col, float* out) {
-#pragma clang fp contract(off)
   const bool ring_r = row < 0 || row >= N, ring_c = col < 0 || col >= N;
   if (ring_r && ring_c) {  // a corner: no texel
     const int ir = min(max(row, 0), N - 1), ic = min(max(col, 0), N - 1);
@@ -106,7 +107,6 @@ __device__ __forceinline__ void tap_any(const T* __restrict__ cube, int N, int k
 // the cube's value in the direction X: face, point, taps, blend
 template <typename T>
 __device__ __forceinline__ void cube_sample(const T* __restrict__ cube, int N, float X0, float X1, float X2, float* out) {
-#pragma clang fp contract(off)
   const float ax = fabsf(X0), ay = fabsf(X1), az = fabsf(X2);
   int k;
   float xr, xd, xn;
@@ -149,51 +149,16 @@ __device__ __forceinline__ void cube_sample(const T* __restrict__ cube, int N, f
   }
 }
 
-// Q = Y(yaw) R_pitch(pitch) R_roll(roll), row major: pano_rotate.hip's lines
-__device__ __forceinline__ void world_rotation(float roll, float pitch, float yaw, float* Q) {
-#pragma clang fp contract(off)
-  float R[9], sy, cy;
-  cam_rotation(roll, pitch, R);
-  sincosf(yaw, &sy, &cy);
-  for (int k = 0; k < 3; ++k) {
-    Q[k] = fmaf(cy, R[k], sy * R[6 + k]);
-    Q[3 + k] = R[3 + k];
-    Q[6 + k] = fmaf(cy, R[6 + k], -(sy * R[k]));
-  }
-}
-
-// offset of sub-sample k of S inside its pixel: 1/2 exactly at S = 1
-__device__ __forceinline__ float sub_offset(int k, float fS) { return ((float)k + 0.5f) / fS; }
-
-// the image of 4 adjacent pixels of a row, each the mean of its n summed samples (0 without one): 12 / 48 bytes with `vec`, otherwise store_px
+// ---------------------------------------------------------------- the two models of gather_ss.h: an empty pixel is 0, nothing is stored beside the image
 template <typename T>
-__device__ __forceinline__ void store_means(T* __restrict__ out, int vec, int col0, int W, const float (*acc)[3], const int* n) {
-  float img[4][3];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float fn = (float)n[k];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) img[k][c] = n[k] > 0 ? acc[k][c] / fn : 0.f;
-  }
-  if (vec) {
-    if constexpr (sizeof(T) == 1) {
-      uint32_t w[3] = {0u, 0u, 0u};
-#pragma unroll
-      for (int e = 0; e < 12; ++e) w[e / 4] |= round_u8(img[e / 3][e % 3]) << (8 * (e % 4));
-      uint32_t* o = reinterpret_cast<uint32_t*>(out);
-      o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
-    } else {
-      store_rgb4(out, img);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (col0 + k >= W) break;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) store_px(out + 3 * k + ch, img[k][ch]);
-    }
-  }
-}
+struct CubeSource {  // what both keep per thread
+  const T* __restrict__ cube;
+  const int N;
+  template <class Batch>
+  __device__ __forceinline__ CubeSource(const Batch& b, int i) : cube(static_cast<const T*>(b.src.p[i])), N(b.src.H[i]) {}
+  __device__ __forceinline__ float empty() const { return 0.f; }
+  __device__ __forceinline__ void finish(int, int, size_t, const int*) const {}
+};
 
 struct CubeCropConsts {
   float Q[9];  // camera -> world, row major
@@ -201,145 +166,83 @@ struct CubeCropConsts {
   int ok;      // 0: a non-finite parameter
 };
 
+// views of cameras: pf_pano_crop's ray (usm_ray_exact), turned into the world by Q
+template <typename T>
+struct CubeCrop : CubeSource<T> {
+  using Texel = T;
+  using Batch = CubeCropBatch;
+  using Consts = CubeCropConsts;
+
+  static __device__ __forceinline__ void setup(const Batch& cb, int out_i, Consts* c) {
+    const float* cam = cb.cam + (size_t)out_i * 7;
+    world_rotation(cam[0], cam[1], cam[2], c->Q);
+    c->invF = 1.f / (cam[3] * (float)cb.d.H);
+    c->Cx = (cam[4] + 0.5f) * (float)cb.d.W;
+    c->Cy = (cam[5] + 0.5f) * (float)cb.d.H;
+    c->xi = cam[6];
+    c->ok = all_finite(cam, 7) ? 1 : 0;
+  }
+
+  const Consts& cc;
+  const float xi, k1;
+  __device__ __forceinline__ CubeCrop(const Batch& b, const Consts& c, int i) : CubeSource<T>(b, i), cc(c), xi(c.xi), k1(1.f - c.xi * c.xi) {}
+
+  __device__ __forceinline__ bool ok() const { return cc.ok != 0; }
+  __device__ __forceinline__ float row_term(int row, float off) const { return ((float)row + off - cc.Cy) * cc.invF; }
+  __device__ __forceinline__ bool sample(float y, int col, float off, float* px) const {
+    float C[3], X[3];
+    if (!usm_ray_exact(((float)col + off - cc.Cx) * cc.invF, y, xi, k1, C)) return false;
+    rotate_exact(cc.Q, C[0], C[1], C[2], X);
+    cube_sample(this->cube, this->N, X[0], X[1], X[2], px);
+    return true;
+  }
+};
+
 struct CubePanoConsts {
   float A[9];  // output direction -> world direction, row major
   int ok;      // 0: a non-finite angle
 };
 
+// panoramas: pf_pano_rotate's pixel -> direction (pano_row, pano_direction), X = A D
+template <typename T>
+struct CubePano : CubeSource<T> {
+  using Texel = T;
+  using Batch = CubePanoBatch;
+  using Consts = CubePanoConsts;
+
+  static __device__ __forceinline__ void setup(const Batch& cb, int out_i, Consts* c) {
+    const float* rot = cb.rot + (size_t)out_i * 3;
+    pano_rotation(rot, cb.inverse, c->A);
+    c->ok = all_finite(rot, 3) ? 1 : 0;
+  }
+
+  const Consts& cc;
+  const int H, W;
+  __device__ __forceinline__ CubePano(const Batch& b, const Consts& c, int i) : CubeSource<T>(b, i), cc(c), H(b.d.H), W(b.d.W) {}
+
+  __device__ __forceinline__ bool ok() const { return cc.ok != 0; }
+  __device__ __forceinline__ PanoRow row_term(int row, float off) const { return pano_row(row, off, H); }
+  __device__ __forceinline__ bool sample(const PanoRow& r, int col, float off, float* px) const {
+    float so, co, D[3], X[3];
+    pano_direction(r, col, off, W, D, &so, &co);
+    rotate_exact(cc.A, D[0], D[1], D[2], X);
+    cube_sample(this->cube, this->N, X[0], X[1], X[2], px);
+    return true;
+  }
+};
+
 }  // namespace
 
 template <typename T>
-__global__ __launch_bounds__(256) void cube_crop_kernel(CubeCropBatch cb) {
-#pragma clang fp contract(off)
-  __shared__ CubeCropConsts cc;
-  const int out_i = blockIdx.y;
-  const int H = cb.d.H, W = cb.d.W;
-  if (threadIdx.x == 0) {
-    const float* cam = cb.cam + (size_t)out_i * 7;
-    const float roll = cam[0], pitch = cam[1], yaw = cam[2], f = cam[3], rcx = cam[4], rcy = cam[5], xi = cam[6];
-    world_rotation(roll, pitch, yaw, cc.Q);
-    cc.invF = 1.f / (f * (float)H);
-    cc.Cx = (rcx + 0.5f) * (float)W;
-    cc.Cy = (rcy + 0.5f) * (float)H;
-    cc.xi = xi;
-    cc.ok = (isfinite(roll) && isfinite(pitch) && isfinite(yaw) && isfinite(f) && isfinite(rcx) && isfinite(rcy) && isfinite(xi)) ? 1 : 0;
-  }
-  __syncthreads();
-  const int tpr = cb.d.tpr;  // threads per tile row; the tile is (4 tpr) x (256 / tpr) pixels
-  const int tile_x = blockIdx.x % cb.d.tiles_x, tile_y = blockIdx.x / cb.d.tiles_x;
-  const int row = tile_y * (256 / tpr) + threadIdx.x / tpr;
-  const int col0 = tile_x * 4 * tpr + (threadIdx.x % tpr) * 4;
-  if (row >= H || col0 >= W) return;
-  const T* __restrict__ cube = static_cast<const T*>(cb.src.p[out_i]);
-  const int N = cb.src.H[out_i];
-  const float xi = cc.xi, k1 = 1.f - xi * xi;
-  const int S = cc.ok ? cb.samples : 0;  // a non-finite parameter: no sub-sample, no load
-  const float fS = (float)cb.samples;
-
-  float acc[4][3];
-  int n[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    acc[k][0] = acc[k][1] = acc[k][2] = -0.f;
-    n[k] = 0;
-  }
-  for (int i = 0; i < S; ++i) {
-    const float y = ((float)row + sub_offset(i, fS) - cc.Cy) * cc.invF;
-    for (int j = 0; j < S; ++j) {
-      const float oj = sub_offset(j, fS);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int col = col0 + k;
-        if (col >= W) continue;
-        // pf_pano_crop's ray: rho^2, disc, eta, X = (eta x, eta y, eta - xi)
-        const float x = ((float)col + oj - cc.Cx) * cc.invF;
-        const float r2 = fmaf(x, x, y * y);
-        const float disc = fmaf(k1, r2, 1.f);
-        if (!(disc >= 0.f)) continue;
-        const float eta = (xi + sqrtf(disc)) / (1.f + r2);
-        const float C0 = eta * x, C1 = eta * y, C2 = eta - xi;
-        const float X0 = fmaf(cc.Q[2], C2, fmaf(cc.Q[1], C1, cc.Q[0] * C0));
-        const float X1 = fmaf(cc.Q[5], C2, fmaf(cc.Q[4], C1, cc.Q[3] * C0));
-        const float X2 = fmaf(cc.Q[8], C2, fmaf(cc.Q[7], C1, cc.Q[6] * C0));
-        float px[3];
-        cube_sample(cube, N, X0, X1, X2, px);
-        acc[k][0] += px[0]; acc[k][1] += px[1]; acc[k][2] += px[2];
-        ++n[k];
-      }
-    }
-  }
-  const size_t pix = (size_t)out_i * ((size_t)H * W) + (size_t)row * W + col0;
-  store_means(static_cast<T*>(cb.img) + pix * 3, cb.d.vec, col0, W, acc, n);
-}
+__global__ __launch_bounds__(256) void cube_crop_kernel(CubeCropBatch cb) { gather_ss<CubeCrop<T>>(cb); }
 
 template <typename T>
-__global__ __launch_bounds__(256) void cube_to_pano_kernel(CubePanoBatch cb) {
-#pragma clang fp contract(off)
-  __shared__ CubePanoConsts cc;
-  const int out_i = blockIdx.y;
-  const int H = cb.d.H, W = cb.d.W;
-  if (threadIdx.x == 0) {
-    const float* rot = cb.rot + (size_t)out_i * 3;
-    float Q[9];
-    world_rotation(rot[0], rot[1], rot[2], Q);
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) cc.A[3 * i + j] = cb.inverse ? Q[3 * j + i] : Q[3 * i + j];
-    cc.ok = (isfinite(rot[0]) && isfinite(rot[1]) && isfinite(rot[2])) ? 1 : 0;
-  }
-  __syncthreads();
-  const int tpr = cb.d.tpr;  // threads per tile row; the tile is (4 tpr) x (256 / tpr) pixels
-  const int tile_x = blockIdx.x % cb.d.tiles_x, tile_y = blockIdx.x / cb.d.tiles_x;
-  const int row = tile_y * (256 / tpr) + threadIdx.x / tpr;
-  const int col0 = tile_x * 4 * tpr + (threadIdx.x % tpr) * 4;
-  if (row >= H || col0 >= W) return;
-  const T* __restrict__ cube = static_cast<const T*>(cb.src.p[out_i]);
-  const int N = cb.src.H[out_i];
-  const int S = cc.ok ? cb.samples : 0;  // a non-finite angle: no sub-sample, no load
-  const float fS = (float)cb.samples;
+__global__ __launch_bounds__(256) void cube_to_pano_kernel(CubePanoBatch cb) { gather_ss<CubePano<T>>(cb); }
 
-  float acc[4][3];
-  int n[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    acc[k][0] = acc[k][1] = acc[k][2] = -0.f;
-    n[k] = 0;
-  }
-  for (int i = 0; i < S; ++i) {
-    float sl, cl;  // pf_pano_rotate's direction of a pixel: the row's latitude once per i
-    sincosf((0.5f - ((float)row + sub_offset(i, fS)) / (float)H) * kPi, &sl, &cl);
-    for (int j = 0; j < S; ++j) {
-      const float oj = sub_offset(j, fS);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int col = col0 + k;
-        if (col >= W) continue;
-        float so, co;
-        sincosf((((float)col + oj) / (float)W - 0.5f) * (2.f * kPi), &so, &co);
-        const float D0 = cl * so, D1 = -sl, D2 = cl * co;
-        const float X0 = fmaf(cc.A[2], D2, fmaf(cc.A[1], D1, cc.A[0] * D0));
-        const float X1 = fmaf(cc.A[5], D2, fmaf(cc.A[4], D1, cc.A[3] * D0));
-        const float X2 = fmaf(cc.A[8], D2, fmaf(cc.A[7], D1, cc.A[6] * D0));
-        float px[3];
-        cube_sample(cube, N, X0, X1, X2, px);
-        acc[k][0] += px[0]; acc[k][1] += px[1]; acc[k][2] += px[2];
-        ++n[k];
-      }
-    }
-  }
-  const size_t pix = (size_t)out_i * ((size_t)H * W) + (size_t)row * W + col0;
-  store_means(static_cast<T*>(cb.img) + pix * 3, cb.d.vec, col0, W, acc, n);
-}
-
-void launch_cube_crop(const CubeCropBatch& cb, int dtype, hipStream_t s) {
-  const dim3 grid((unsigned)(cb.d.tiles_x * cb.d.tiles_y), (unsigned)cb.d.n), block(256);
-  if (dtype == PF_PANO_U8) hipLaunchKernelGGL(cube_crop_kernel<uint8_t>, grid, block, 0, s, cb);
-  else hipLaunchKernelGGL(cube_crop_kernel<float>, grid, block, 0, s, cb);
-}
+void launch_cube_crop(const CubeCropBatch& cb, int dtype, hipStream_t s) { launch_ss(cube_crop_kernel<uint8_t>, cube_crop_kernel<float>, cb, dtype, s); }
 
 void launch_cube_to_pano(const CubePanoBatch& cb, int dtype, hipStream_t s) {
-  const dim3 grid((unsigned)(cb.d.tiles_x * cb.d.tiles_y), (unsigned)cb.d.n), block(256);
-  if (dtype == PF_PANO_U8) hipLaunchKernelGGL(cube_to_pano_kernel<uint8_t>, grid, block, 0, s, cb);
-  else hipLaunchKernelGGL(cube_to_pano_kernel<float>, grid, block, 0, s, cb);
+  launch_ss(cube_to_pano_kernel<uint8_t>, cube_to_pano_kernel<float>, cb, dtype, s);
 }
 
 }  // namespace pf

@@ -1,82 +1,24 @@
 // The supersampled forms of the three one-source gathers (include/pf_hip.h pf_pano_crop_ss / pf_reproject_ss / pf_pano_rotate_ss, DESIGN.md
 // section 25): antialiasing for crops, re-projections and rotations that minify.  VALU and memory bound, no MFMA, no atomics.
-// An output pixel is the mean of the valid ones of S x S sub-samples, S = `samples` in [1, PF_GATHER_MAX_SAMPLES].  Sub-sample (i, j) of pixel (row, col)
-// sits at (a, b) = (col + (j + 1/2) / S, row + (i + 1/2) / S) and is its gather's per-sample model at that point, unchanged: ray, validity, source
-// coordinate, tap rule and blend order are those of pano_crop.hip, reproject.hip and pano_rotate.hip, whose few lines per sample are restated here
-// (their text does not change).  The fp32 sum runs over the valid sub-samples i-major, then j, from -0 (so that one sample is itself, whatever its sign),
-// and is divided by their count as sum / (float)n; a pixel without a valid sub-sample is 0 (crop, rotation) or `fill` (re-projection).  At S = 1 the
-// offsets are 1/2 exactly and every kernel gives the bits of its parent (tests/test_gpu_gather_samples.py).
-// What describes the pixel and not its footprint is taken at the pixel centre with the parent's code: the labels of the crop and of the rotation, the
-// map of the re-projection.  With an even S the centre is not itself a sub-sample.  The mask of the re-projection is 1 iff a sub-sample is valid.
+// The sample loop, the mean and the stores are gather_ss.h's; the re-projection and the rotation are models plugged into it, the crop keeps its loop
+// in its own text and calls gather_ss.h's helpers (DESIGN.md section 31 says why).  A sub-sample is its gather's per-sample model at its point,
+// unchanged: ray, validity, source coordinate, tap rule and blend order are those of pano_crop.hip, reproject.hip and pano_rotate.hip, with the
+// pixel centre's 1/2 a parameter.  A pixel without a valid sub-sample is 0 (crop, rotation) or `fill` (re-projection).  At S = 1 the offsets are 1/2 exactly and every kernel gives the bits of its parent (tests/test_gpu_gather_samples.py).
+// What describes the pixel and not its footprint is taken at the pixel centre with the parent's formulas: the labels of the crop and of the rotation,
+// the map of the re-projection.  With an even S the centre is not itself a sub-sample.  The mask of the re-projection is 1 iff a sub-sample is valid.
 //   pano_crop_ss_kernel<T, LABELS>, reproject_ss_kernel<T, EXTRAS>, pano_rotate_ss_kernel<T, LABELS>
-//       the parents' shape: grid (tiles per output) x (outputs of the group), 256 threads, a 64 x 16 tile, 4 adjacent pixels of a row per thread, lane 0
-//       computes the output's constants into LDS once per block, 64-bit offsets, every tap index forced into the source, vector stores with
-//       GatherDims::vec.  S is a run-time loop: i outermost (the row's terms once per i), then j (the column offset once per j), then the thread's 4
-//       pixels unrolled as in the parents, so that the body is the parents' body and one kernel serves every S (DESIGN.md section 25 says why).
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/pf_hip.h"
 #include "cam_model.h"
-#include "gather.h"
+#include "gather_ss.h"
 
 namespace pf {
 
 namespace {
 
-constexpr float kInv2Pi = 0.15915494309189535f, kInvPi = 0.3183098861837907f, kPi = 3.14159265358979323846f, kRad2Deg = 57.29577951308232f;
-
-// offset of sub-sample k of S inside its pixel: 1/2 exactly at S = 1
-__device__ __forceinline__ float sub_offset(int k, float fS) { return ((float)k + 0.5f) / fS; }
-
-// the mean of n >= 1 summed samples, or `empty`
-__device__ __forceinline__ void mean_of(const float* acc, int n, float empty, float* out) {
-  const float fn = (float)n;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) out[c] = n > 0 ? acc[c] / fn : empty;
-}
-
-// the image of 4 adjacent pixels of a row: 12 / 48 bytes with `vec`, otherwise store_px for the pixels inside the row
-template <typename T>
-__device__ __forceinline__ void store_image(T* __restrict__ out, int vec, int col0, int W, const float (*img)[3]) {
-  if (vec) {
-    if constexpr (sizeof(T) == 1) {
-      uint32_t w[3] = {0u, 0u, 0u};
-#pragma unroll
-      for (int e = 0; e < 12; ++e) w[e / 4] |= round_u8(img[e / 3][e % 3]) << (8 * (e % 4));
-      uint32_t* o = reinterpret_cast<uint32_t*>(out);
-      o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
-    } else {
-      store_rgb4(out, img);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (col0 + k >= W) break;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) store_px(out + 3 * k + ch, img[k][ch]);
-    }
-  }
-}
-
-// the labels of 4 adjacent pixels of output `out_i`: 16-byte vectors with `vec`, otherwise scalars for the pixels inside the row
-__device__ __forceinline__ void store_labels(float* up, float* lat, int vec, int out_i, int H, int W, int row, int col0, const float* ux, const float* uy,
-                                             const float* la) {
-  const size_t npx = (size_t)H * W, l = (size_t)out_i * npx + (size_t)row * W + col0;
-  if (vec) {
-    *reinterpret_cast<float4*>(up + l + (size_t)out_i * npx) = make_float4(ux[0], ux[1], ux[2], ux[3]);
-    *reinterpret_cast<float4*>(up + l + (size_t)out_i * npx + npx) = make_float4(uy[0], uy[1], uy[2], uy[3]);
-    *reinterpret_cast<float4*>(lat + l) = make_float4(la[0], la[1], la[2], la[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (col0 + k >= W) break;
-      up[l + k + (size_t)out_i * npx] = ux[k];
-      up[l + k + (size_t)out_i * npx + npx] = uy[k];
-      lat[l + k] = la[k];
-    }
-  }
-}
+constexpr float kInv2Pi = 0.15915494309189535f, kInvPi = 0.3183098861837907f, kRad2Deg = 57.29577951308232f;
 
 // ---------------------------------------------------------------- pano_crop.hip's constants
 struct CropConsts {
@@ -86,14 +28,111 @@ struct CropConsts {
   PinholeFields pin;  // the xi == 0 labels
 };
 
-// ---------------------------------------------------------------- reproject.hip's constants
+// ---------------------------------------------------------------- reproject.hip's model
 struct ReprojConsts {
   float M[9];  // destination camera -> source camera, row major
   float invFd, Cxd, Cyd, xid;
   float Fs, Cxs, Cys, xis, zmin;
 };
 
-// ---------------------------------------------------------------- pano_rotate.hip's constants and per-pixel function, the pixel centre's 1/2 a parameter
+// M = Rs^T Tm, reproject.hip's `Rs[i] * Tm[j] + Rs[3 + i] * Tm[3 + j] + Rs[6 + i] * Tm[6 + j]` with the rounding steps spelled out.  The sum of
+// three products leaves the choice of the one that stays a product to the compiler: in reproject_kernel it is the middle one in the rows i = 0
+// and i = 2 and the first one in the row i = 1 (Rs[1] = -sin(roll) makes that sum a difference); inside gather_ss<M> three entries came out
+// differently, so reproject_kernel's arrangement is written out here
+__device__ __forceinline__ void reproj_matrix(const float* Rs, const float* Tm, float* M) {
+#pragma clang fp contract(off)
+  for (int j = 0; j < 3; ++j) {
+    M[j] = fmaf(Rs[6], Tm[6 + j], fmaf(Rs[0], Tm[j], Rs[3] * Tm[3 + j]));
+    M[3 + j] = fmaf(Rs[7], Tm[6 + j], fmaf(Rs[4], Tm[3 + j], Rs[1] * Tm[j]));
+    M[6 + j] = fmaf(Rs[8], Tm[6 + j], fmaf(Rs[2], Tm[j], Rs[5] * Tm[3 + j]));
+  }
+}
+
+template <typename T, bool EXTRAS>
+struct ReprojSs {
+  using Texel = T;
+  using Batch = ReprojSsBatch;
+  using Consts = ReprojConsts;
+
+  static __device__ __forceinline__ void setup(const Batch& rb, int o, Consts* c) {
+    const int H = rb.d.H, W = rb.d.W, Hs = rb.src.H[o], Ws = rb.src.W[o];
+    const float* cs = rb.cam_src + (size_t)o * 7;
+    const float* cd = rb.cam_dst + (size_t)o * 7;
+    float Rs[9], Rd[9], sy, cy;
+    cam_rotation(cs[0], cs[1], Rs);
+    cam_rotation(cd[0], cd[1], Rd);
+    sincosf(cd[2] - cs[2], &sy, &cy);
+    float Tm[9];  // Y(yaw_d - yaw_s) R_d
+    for (int j = 0; j < 3; ++j) {
+      Tm[j] = cy * Rd[j] + sy * Rd[6 + j];
+      Tm[3 + j] = Rd[3 + j];
+      Tm[6 + j] = cy * Rd[6 + j] - sy * Rd[j];
+    }
+    reproj_matrix(Rs, Tm, c->M);
+    c->invFd = 1.f / (cd[3] * (float)H);
+    c->Cxd = (cd[4] + 0.5f) * (float)W;
+    c->Cyd = (cd[5] + 0.5f) * (float)H;
+    c->xid = cd[6];
+    c->Fs = cs[3] * (float)Hs;
+    c->Cxs = (cs[4] + 0.5f) * (float)Ws;
+    c->Cys = (cs[5] + 0.5f) * (float)Hs;
+    c->xis = cs[6];
+    c->zmin = usm_z_min(cs[6]);
+  }
+
+  const Batch& rb;
+  const Consts& cc;
+  const int o;
+  const T* __restrict__ src;
+  const int Hs, Ws;
+  __device__ __forceinline__ ReprojSs(const Batch& b, const Consts& c, int i)
+      : rb(b), cc(c), o(i), src(static_cast<const T*>(b.src.p[i])), Hs(b.src.H[i]), Ws(b.src.W[i]) {}
+
+  __device__ __forceinline__ bool ok() const { return true; }  // a non-finite camera fails the positive comparisons below, as in the parent
+  __device__ __forceinline__ float empty() const { return rb.fill; }
+  __device__ __forceinline__ float row_term(int row, float off) const { return ((float)row + off - cc.Cyd) * cc.invFd; }
+
+  // reproject.hip's steps from the destination point (col + off, .) with normalised row y to the source point (a, b); false where not visible
+  __device__ __forceinline__ bool source_point(float y, int col, float off, float* a, float* b) const {
+    float X[3], Xs[3], xs, ys;
+    if (!usm_ray(((float)col + off - cc.Cxd) * cc.invFd, y, cc.xid, X)) return false;
+    to_world(cc.M, X, Xs);
+    if (!(Xs[2] > cc.zmin)) return false;
+    usm_project(Xs, cc.xis, &xs, &ys);
+    *a = cc.Fs * xs + cc.Cxs;
+    *b = cc.Fs * ys + cc.Cys;
+    return true;
+  }
+
+  __device__ __forceinline__ bool sample(float y, int col, float off, float* px) const {
+    float a, b;
+    if (!source_point(y, col, off, &a, &b)) return false;
+    if (!(a >= 0.f && a <= (float)Ws && b >= 0.f && b <= (float)Hs)) return false;  // false for NaN and infinities: no load without a point inside the source
+    sample_clamped(src, Hs, Ws, a - 0.5f, b - 0.5f, px);
+    return true;
+  }
+
+  // the mask, and the map, which is the pixel centre's: reproject.hip's steps at (col + 1/2, row + 1/2)
+  __device__ __forceinline__ void finish(int row, int col0, size_t pix, const int* n) const {
+    if (!EXTRAS) return;
+    const int W = rb.d.W;
+    if (rb.valid) store_mask(rb.valid + pix, rb.d.vec, col0, W, n);
+    if (!rb.map) return;
+    float ma[4], mb[4];
+    const float y = row_term(row, 0.5f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      ma[k] = mb[k] = __builtin_nanf("");
+      if (col0 + k < W) source_point(y, col0 + k, 0.5f, &ma[k], &mb[k]);  // (a, b) are written where the point is visible
+    }
+    const size_t npx = (size_t)rb.d.H * W;
+    float* m = rb.map + pix + (size_t)o * npx;  // [n][2][H][W]
+    store_plane4(m, rb.d.vec, col0, W, ma);
+    store_plane4(m + npx, rb.d.vec, col0, W, mb);
+  }
+};
+
+// ---------------------------------------------------------------- pano_rotate.hip's model, the pixel centre's 1/2 a parameter
 struct RotConsts {
   float A[9];    // output direction -> source (world) direction, row major
   float g[3];    // world up (0, -1, 0) in the output camera's coordinates: A^T (0, -1, 0)
@@ -101,51 +140,22 @@ struct RotConsts {
   int ok;        // 0: a non-finite angle
 };
 
-// rot = {roll, pitch, yaw} radians
-__device__ __forceinline__ void rot_setup(const float* rot, int inverse, int H, int W, RotConsts* c) {
-#pragma clang fp contract(off)
-  const float roll = rot[0], pitch = rot[1], yaw = rot[2];
-  float R[9], sy, cy, Q[9];
-  cam_rotation(roll, pitch, R);
-  sincosf(yaw, &sy, &cy);
-  // Y(yaw) R, Y = [[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]
-  for (int k = 0; k < 3; ++k) {
-    Q[k] = fmaf(cy, R[k], sy * R[6 + k]);
-    Q[3 + k] = R[3 + k];
-    Q[6 + k] = fmaf(cy, R[6 + k], -(sy * R[k]));
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) c->A[3 * i + j] = inverse ? Q[3 * j + i] : Q[3 * i + j];
-  c->g[0] = -c->A[3]; c->g[1] = -c->A[4]; c->g[2] = -c->A[5];
-  c->kx = (float)W * kInv2Pi;
-  c->ky = (float)H * kInvPi;
-  c->ok = (isfinite(roll) && isfinite(pitch) && isfinite(yaw)) ? 1 : 0;
-}
-
-// sine and cosine of the latitude of the point `off` below the top of row `row`
-__device__ __forceinline__ void row_sincos(int row, float off, int H, float* sl, float* cl) {
-#pragma clang fp contract(off)
-  sincosf((0.5f - ((float)row + off) / (float)H) * kPi, sl, cl);
-}
-
 struct RotPixel {
   float ts, tl;      // longitude and latitude of the source point as fractions: lon_s / 2 pi + 1/2 and 1/2 - lat_s / pi
   float ux, uy, lat; // the labels (LABELS only)
 };
 
-// the point `off` right of the left side of pixel `col` of an H x W output, on a row whose latitude has sine / cosine (sl, cl)
+// the point `off` right of the left side of pixel `col` of an output of W columns, on the row r
 template <bool LABELS>
-__device__ __forceinline__ RotPixel rot_pixel(const RotConsts& c, float sl, float cl, int col, float off, int W) {
+__device__ __forceinline__ RotPixel rot_pixel(const RotConsts& c, const PanoRow& r, int col, float off, int W) {
 #pragma clang fp contract(off)
-  float so, co;
-  sincosf((((float)col + off) / (float)W - 0.5f) * (2.f * kPi), &so, &co);
-  const float D0 = cl * so, D1 = -sl, D2 = cl * co;
-  const float X0 = fmaf(c.A[2], D2, fmaf(c.A[1], D1, c.A[0] * D0));
-  const float X1 = fmaf(c.A[5], D2, fmaf(c.A[4], D1, c.A[3] * D0));
-  const float X2 = fmaf(c.A[8], D2, fmaf(c.A[7], D1, c.A[6] * D0));
-  const float nlat = atan2f(X1, sqrtf(fmaf(X0, X0, X2 * X2)));  // -lat_s
+  const float sl = r.sl, cl = r.cl;
+  float so, co, D[3], X[3];
+  pano_direction(r, col, off, W, D, &so, &co);
+  rotate_exact(c.A, D[0], D[1], D[2], X);
+  const float nlat = atan2f(X[1], sqrtf(fmaf(X[0], X[0], X[2] * X[2])));  // -lat_s
   RotPixel o;
-  o.ts = fmaf(atan2f(X0, X2), kInv2Pi, 0.5f);
+  o.ts = fmaf(atan2f(X[0], X[2]), kInv2Pi, 0.5f);
   o.tl = fmaf(nlat, kInvPi, 0.5f);
   if (LABELS) {
     o.lat = -nlat * kRad2Deg;
@@ -161,8 +171,65 @@ __device__ __forceinline__ RotPixel rot_pixel(const RotConsts& c, float sl, floa
   return o;
 }
 
+template <typename T, bool LABELS>
+struct RotSs {
+  using Texel = T;
+  using Batch = PanoRotSsBatch;
+  using Consts = RotConsts;
+
+  static __device__ __forceinline__ void setup(const Batch& rb, int out_i, Consts* c) {
+#pragma clang fp contract(off)
+    const float* rot = rb.rot + (size_t)out_i * 3;
+    pano_rotation(rot, rb.inverse, c->A);
+    c->g[0] = -c->A[3]; c->g[1] = -c->A[4]; c->g[2] = -c->A[5];
+    c->kx = (float)rb.d.W * kInv2Pi;
+    c->ky = (float)rb.d.H * kInvPi;
+    c->ok = all_finite(rot, 3) ? 1 : 0;
+  }
+
+  const Batch& rb;
+  const Consts& rc;
+  const int out_i;
+  const T* __restrict__ src;
+  const int Hs, Ws;
+  __device__ __forceinline__ RotSs(const Batch& b, const Consts& c, int i)
+      : rb(b), rc(c), out_i(i), src(static_cast<const T*>(b.src.p[i])), Hs(b.src.H[i]), Ws(b.src.W[i]) {}
+
+  __device__ __forceinline__ bool ok() const { return rc.ok != 0; }
+  __device__ __forceinline__ float empty() const { return 0.f; }
+  __device__ __forceinline__ PanoRow row_term(int row, float off) const { return pano_row(row, off, rb.d.H); }
+
+  __device__ __forceinline__ bool sample(const PanoRow& r, int col, float off, float* px) const {
+    const RotPixel o = rot_pixel<false>(rc, r, col, off, rb.d.W);
+    pf::sample(src, Hs, Ws, fmaf(o.ts, (float)Ws, -0.5f), fmaf(o.tl, (float)Hs, -0.5f), px);
+    return true;
+  }
+
+  // the labels are the pixel centre's: pano_rotate.hip's
+  __device__ __forceinline__ void finish(int row, int col0, size_t pix, const int*) const {
+    if (!LABELS) return;
+    const int W = rb.d.W;
+    float ux[4], uy[4], lat[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ux[k] = uy[k] = lat[k] = __builtin_nanf("");
+    if (rc.ok) {
+      const PanoRow r = row_term(row, 0.5f);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (col0 + k >= W) continue;
+        const RotPixel o = rot_pixel<true>(rc, r, col0 + k, 0.5f, W);
+        ux[k] = o.ux; uy[k] = o.uy; lat[k] = o.lat;
+      }
+    }
+    store_labels(rb.up, rb.lat, rb.d.vec, out_i, (size_t)rb.d.H * W, pix, col0, W, ux, uy, lat);
+  }
+};
+
 }  // namespace
 
+// The crop keeps gather_ss<M>'s loop in its own text: as a model the compiler fused the other product of bilerp_rgb's `(1 - fu) t00 + fu t01`
+// (other bits than pano_crop_kernel's), and with that blend spelled out the kernel was 15 - 20 % slower on the timed crop workload (DESIGN.md
+// section 31).  A change to gather_ss<M>'s loop or rules has to be made here as well
 template <typename T, bool LABELS>
 __global__ __launch_bounds__(256) void pano_crop_ss_kernel(PanoSsBatch pb) {
   __shared__ CropConsts cc;
@@ -251,234 +318,28 @@ __global__ __launch_bounds__(256) void pano_crop_ss_kernel(PanoSsBatch pb) {
 
   const size_t npx = (size_t)H * W, pix = (size_t)crop * npx + (size_t)row * W + col0;
   store_image(static_cast<T*>(pb.img) + pix * 3, pb.d.vec, col0, W, img);
-  if (LABELS) store_labels(pb.up, pb.lat, pb.d.vec, crop, H, W, row, col0, ux, uy, lat);
+  if (LABELS) store_labels(pb.up, pb.lat, pb.d.vec, crop, npx, pix, col0, W, ux, uy, lat);
 }
 
 template <typename T, bool EXTRAS>
-__global__ __launch_bounds__(256) void reproject_ss_kernel(ReprojSsBatch rb) {
-  __shared__ ReprojConsts cc;
-  const int o = blockIdx.y;
-  const int H = rb.d.H, W = rb.d.W;
-  const int Hs = rb.src.H[o], Ws = rb.src.W[o];
-  if (threadIdx.x == 0) {
-    const float* cs = rb.cam_src + (size_t)o * 7;
-    const float* cd = rb.cam_dst + (size_t)o * 7;
-    float Rs[9], Rd[9], sy, cy;
-    cam_rotation(cs[0], cs[1], Rs);
-    cam_rotation(cd[0], cd[1], Rd);
-    sincosf(cd[2] - cs[2], &sy, &cy);
-    float Tm[9];  // Y(yaw_d - yaw_s) R_d
-    for (int j = 0; j < 3; ++j) {
-      Tm[j] = cy * Rd[j] + sy * Rd[6 + j];
-      Tm[3 + j] = Rd[3 + j];
-      Tm[6 + j] = cy * Rd[6 + j] - sy * Rd[j];
-    }
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) cc.M[3 * i + j] = Rs[i] * Tm[j] + Rs[3 + i] * Tm[3 + j] + Rs[6 + i] * Tm[6 + j];
-    cc.invFd = 1.f / (cd[3] * (float)H);
-    cc.Cxd = (cd[4] + 0.5f) * (float)W;
-    cc.Cyd = (cd[5] + 0.5f) * (float)H;
-    cc.xid = cd[6];
-    cc.Fs = cs[3] * (float)Hs;
-    cc.Cxs = (cs[4] + 0.5f) * (float)Ws;
-    cc.Cys = (cs[5] + 0.5f) * (float)Hs;
-    cc.xis = cs[6];
-    cc.zmin = usm_z_min(cs[6]);
-  }
-  __syncthreads();
-  const int tpr = rb.d.tpr;  // threads per tile row; the tile is (4 tpr) x (256 / tpr) pixels
-  const int tile_x = blockIdx.x % rb.d.tiles_x, tile_y = blockIdx.x / rb.d.tiles_x;
-  const int row = tile_y * (256 / tpr) + threadIdx.x / tpr;
-  const int col0 = tile_x * 4 * tpr + (threadIdx.x % tpr) * 4;
-  if (row >= H || col0 >= W) return;
-  const T* __restrict__ src = static_cast<const T*>(rb.src.p[o]);
-  const float wmax = (float)Ws, hmax = (float)Hs;
-  const int S = rb.samples;
-  const float fS = (float)S;
-
-  float acc[4][3];
-  int n[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    acc[k][0] = acc[k][1] = acc[k][2] = -0.f;
-    n[k] = 0;
-  }
-  for (int i = 0; i < S; ++i) {
-    const float y = ((float)row + sub_offset(i, fS) - cc.Cyd) * cc.invFd;
-    for (int j = 0; j < S; ++j) {
-      const float oj = sub_offset(j, fS);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int col = col0 + k;
-        if (col >= W) continue;
-        float X[3];
-        if (!usm_ray(((float)col + oj - cc.Cxd) * cc.invFd, y, cc.xid, X)) continue;
-        float Xs[3];
-        to_world(cc.M, X, Xs);
-        if (!(Xs[2] > cc.zmin)) continue;
-        float xs, ys;
-        usm_project(Xs, cc.xis, &xs, &ys);
-        const float a = cc.Fs * xs + cc.Cxs, b = cc.Fs * ys + cc.Cys;
-        if (a >= 0.f && a <= wmax && b >= 0.f && b <= hmax) {  // false for NaN and infinities: no load without a point inside the source
-          float px[3];
-          sample_clamped(src, Hs, Ws, a - 0.5f, b - 0.5f, px);
-          acc[k][0] += px[0]; acc[k][1] += px[1]; acc[k][2] += px[2];
-          ++n[k];
-        }
-      }
-    }
-  }
-
-  float img[4][3], ma[4], mb[4];
-  uint32_t ok[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    mean_of(acc[k], n[k], rb.fill, img[k]);
-    ok[k] = n[k] > 0 ? 1u : 0u;
-    ma[k] = mb[k] = __builtin_nanf("");
-  }
-  if (EXTRAS && rb.map) {  // the map is the pixel centre's: reproject.hip's steps at (col + 1/2, row + 1/2)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int col = col0 + k;
-      if (col >= W) continue;
-      float X[3];
-      if (!usm_ray(((float)col + 0.5f - cc.Cxd) * cc.invFd, ((float)row + 0.5f - cc.Cyd) * cc.invFd, cc.xid, X)) continue;
-      float Xs[3];
-      to_world(cc.M, X, Xs);
-      if (!(Xs[2] > cc.zmin)) continue;
-      float xs, ys;
-      usm_project(Xs, cc.xis, &xs, &ys);
-      ma[k] = cc.Fs * xs + cc.Cxs;
-      mb[k] = cc.Fs * ys + cc.Cys;
-    }
-  }
-
-  const size_t npx = (size_t)H * W, pix = (size_t)o * npx + (size_t)row * W + col0;
-  store_image(static_cast<T*>(rb.img) + pix * 3, rb.d.vec, col0, W, img);
-  if (EXTRAS) {
-    if (rb.d.vec) {  // 4 mask bytes and two 16-byte map vectors
-      if (rb.valid) *reinterpret_cast<uint32_t*>(rb.valid + pix) = ok[0] | ok[1] << 8 | ok[2] << 16 | ok[3] << 24;
-      if (rb.map) {
-        float* m = rb.map + pix + (size_t)o * npx;  // [n][2][H][W]
-        *reinterpret_cast<float4*>(m) = make_float4(ma[0], ma[1], ma[2], ma[3]);
-        *reinterpret_cast<float4*>(m + npx) = make_float4(mb[0], mb[1], mb[2], mb[3]);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (col0 + k >= W) break;
-        if (rb.valid) rb.valid[pix + k] = (uint8_t)ok[k];
-        if (rb.map) {
-          rb.map[pix + (size_t)o * npx + k] = ma[k];
-          rb.map[pix + (size_t)o * npx + npx + k] = mb[k];
-        }
-      }
-    }
-  }
-}
+__global__ __launch_bounds__(256) void reproject_ss_kernel(ReprojSsBatch rb) { gather_ss<ReprojSs<T, EXTRAS>>(rb); }
 
 template <typename T, bool LABELS>
-__global__ __launch_bounds__(256) void pano_rotate_ss_kernel(PanoRotSsBatch rb) {
-  __shared__ RotConsts rc;
-  const int out_i = blockIdx.y;
-  const int H = rb.d.H, W = rb.d.W;
-  if (threadIdx.x == 0) rot_setup(rb.rot + (size_t)out_i * 3, rb.inverse, H, W, &rc);
-  __syncthreads();
-  const int tpr = rb.d.tpr;  // threads per tile row; the tile is (4 tpr) x (256 / tpr) pixels
-  const int tile_x = blockIdx.x % rb.d.tiles_x, tile_y = blockIdx.x / rb.d.tiles_x;
-  const int row = tile_y * (256 / tpr) + threadIdx.x / tpr;
-  const int col0 = tile_x * 4 * tpr + (threadIdx.x % tpr) * 4;
-  if (row >= H || col0 >= W) return;
-  const T* __restrict__ src = static_cast<const T*>(rb.src.p[out_i]);
-  const int Hs = rb.src.H[out_i], Ws = rb.src.W[out_i];
-  const int S = rc.ok ? rb.samples : 0;  // a non-finite angle: no sub-sample, no load
-  const float fS = (float)rb.samples;
-
-  float acc[4][3];
-  int n[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    acc[k][0] = acc[k][1] = acc[k][2] = -0.f;
-    n[k] = 0;
-  }
-  for (int i = 0; i < S; ++i) {
-    float sl, cl;
-    row_sincos(row, sub_offset(i, fS), H, &sl, &cl);
-    for (int j = 0; j < S; ++j) {
-      const float oj = sub_offset(j, fS);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int col = col0 + k;
-        if (col >= W) continue;
-        const RotPixel o = rot_pixel<false>(rc, sl, cl, col, oj, W);
-        float px[3];
-        sample(src, Hs, Ws, fmaf(o.ts, (float)Ws, -0.5f), fmaf(o.tl, (float)Hs, -0.5f), px);
-        acc[k][0] += px[0]; acc[k][1] += px[1]; acc[k][2] += px[2];
-        ++n[k];
-      }
-    }
-  }
-
-  float img[4][3], ux[4], uy[4], lat[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    mean_of(acc[k], n[k], 0.f, img[k]);
-    ux[k] = uy[k] = lat[k] = __builtin_nanf("");
-  }
-  if (LABELS && rc.ok) {  // the labels are the pixel centre's: pano_rotate.hip's
-    float sl, cl;
-    row_sincos(row, 0.5f, H, &sl, &cl);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (col0 + k >= W) continue;
-      const RotPixel o = rot_pixel<true>(rc, sl, cl, col0 + k, 0.5f, W);
-      ux[k] = o.ux; uy[k] = o.uy; lat[k] = o.lat;
-    }
-  }
-
-  const size_t npx = (size_t)H * W, pix = (size_t)out_i * npx + (size_t)row * W + col0;
-  store_image(static_cast<T*>(rb.img) + pix * 3, rb.d.vec, col0, W, img);
-  if (LABELS) store_labels(rb.up, rb.lat, rb.d.vec, out_i, H, W, row, col0, ux, uy, lat);
-}
-
-template <class Batch>
-static dim3 ss_grid(const Batch& b) { return dim3((unsigned)(b.d.tiles_x * b.d.tiles_y), (unsigned)b.d.n); }
+__global__ __launch_bounds__(256) void pano_rotate_ss_kernel(PanoRotSsBatch rb) { gather_ss<RotSs<T, LABELS>>(rb); }
 
 void launch_pano_crop_ss(const PanoSsBatch& pb, int dtype, hipStream_t s) {
-  const dim3 grid = ss_grid(pb), block(256);
-  const bool labels = pb.up != nullptr;
-  if (dtype == PF_PANO_U8) {
-    if (labels) hipLaunchKernelGGL((pano_crop_ss_kernel<uint8_t, true>), grid, block, 0, s, pb);
-    else hipLaunchKernelGGL((pano_crop_ss_kernel<uint8_t, false>), grid, block, 0, s, pb);
-  } else {
-    if (labels) hipLaunchKernelGGL((pano_crop_ss_kernel<float, true>), grid, block, 0, s, pb);
-    else hipLaunchKernelGGL((pano_crop_ss_kernel<float, false>), grid, block, 0, s, pb);
-  }
+  if (pb.up) launch_ss(pano_crop_ss_kernel<uint8_t, true>, pano_crop_ss_kernel<float, true>, pb, dtype, s);
+  else launch_ss(pano_crop_ss_kernel<uint8_t, false>, pano_crop_ss_kernel<float, false>, pb, dtype, s);
 }
 
 void launch_reproject_ss(const ReprojSsBatch& rb, int dtype, hipStream_t s) {
-  const dim3 grid = ss_grid(rb), block(256);
-  const bool extras = rb.valid != nullptr || rb.map != nullptr;
-  if (dtype == PF_PANO_U8) {
-    if (extras) hipLaunchKernelGGL((reproject_ss_kernel<uint8_t, true>), grid, block, 0, s, rb);
-    else hipLaunchKernelGGL((reproject_ss_kernel<uint8_t, false>), grid, block, 0, s, rb);
-  } else {
-    if (extras) hipLaunchKernelGGL((reproject_ss_kernel<float, true>), grid, block, 0, s, rb);
-    else hipLaunchKernelGGL((reproject_ss_kernel<float, false>), grid, block, 0, s, rb);
-  }
+  if (rb.valid || rb.map) launch_ss(reproject_ss_kernel<uint8_t, true>, reproject_ss_kernel<float, true>, rb, dtype, s);
+  else launch_ss(reproject_ss_kernel<uint8_t, false>, reproject_ss_kernel<float, false>, rb, dtype, s);
 }
 
 void launch_pano_rotate_ss(const PanoRotSsBatch& rb, int dtype, hipStream_t s) {
-  const dim3 grid = ss_grid(rb), block(256);
-  const bool labels = rb.up != nullptr;
-  if (dtype == PF_PANO_U8) {
-    if (labels) hipLaunchKernelGGL((pano_rotate_ss_kernel<uint8_t, true>), grid, block, 0, s, rb);
-    else hipLaunchKernelGGL((pano_rotate_ss_kernel<uint8_t, false>), grid, block, 0, s, rb);
-  } else {
-    if (labels) hipLaunchKernelGGL((pano_rotate_ss_kernel<float, true>), grid, block, 0, s, rb);
-    else hipLaunchKernelGGL((pano_rotate_ss_kernel<float, false>), grid, block, 0, s, rb);
-  }
+  if (rb.up) launch_ss(pano_rotate_ss_kernel<uint8_t, true>, pano_rotate_ss_kernel<float, true>, rb, dtype, s);
+  else launch_ss(pano_rotate_ss_kernel<uint8_t, false>, pano_rotate_ss_kernel<float, false>, rb, dtype, s);
 }
 
 }  // namespace pf

@@ -1,5 +1,7 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
 // gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip, fisheye_gather.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the pasting of objects (composite.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+#include <type_traits>
+
 #include "host_pack.h"
 
 using namespace pf;
@@ -71,83 +73,56 @@ static int gather_run(const GatherKind& g, void (*launch)(const Batch&, int, hip
 
 static uintptr_t misalign(const void* p, uintptr_t mask) { return reinterpret_cast<uintptr_t>(p) & mask; }
 
-int pf_pano_crop(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
-                 const float* d_cam7, int H, int W, void* d_img, float* d_up, float* d_lat, void* stream) {
-  static const GatherKind kind{"pf_pano_crop", "panorama", "crop", 2, "needs at least one panorama (h_pano, h_pano_hw)",
-                               "batch >= 1, h_pano_index, d_cam7 and d_img are required"};
-  const size_t npx = (size_t)H * W;
-  return gather_run(kind, launch_pano_crop, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_cam7 != nullptr, H, W, d_img,
-                    !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr, misalign(d_up, 15) | misalign(d_lat, 15), stream,
-                    [=](PanoBatch& pb, int i0) {
-                      pb.cam = d_cam7 + (size_t)i0 * 7;
-                      pb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
-                      pb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
-                    });
-}
-
-int pf_reproject(int device, int n_src, const void* const* src, const int32_t* src_hw, int dtype, int B, const int32_t* src_index,
-                 const float* d_cam_src7, const float* d_cam_dst7, int H, int W, float fill, void* d_img, uint8_t* d_valid, float* d_map, void* stream) {
-  static const GatherKind kind{"pf_reproject", "source", "output", 1, "needs at least one source image (h_src, h_src_hw)",
-                               "batch >= 1, h_src_index, d_cam_src7, d_cam_dst7 and d_img are required"};
-  const size_t npx = (size_t)H * W;
-  return gather_run(kind, launch_reproject, device, n_src, src, src_hw, dtype, B, src_index, d_cam_src7 && d_cam_dst7, H, W, d_img, nullptr,
-                    misalign(d_valid, 3) | misalign(d_map, 15), stream, [=](ReprojBatch& rb, int i0) {
-                      rb.fill = fill;
-                      rb.cam_src = d_cam_src7 + (size_t)i0 * 7;
-                      rb.cam_dst = d_cam_dst7 + (size_t)i0 * 7;
-                      rb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
-                      rb.map = d_map ? d_map + (size_t)i0 * 2 * npx : nullptr;
-                    });
-}
-
-int pf_pano_rotate(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
-                   const float* d_rot3, int inverse, int H, int W, void* d_img, float* d_up, float* d_lat, void* stream) {
-  static const GatherKind kind{"pf_pano_rotate", "panorama", "output", 2, "needs at least one panorama (h_pano, h_pano_hw)",
-                               "batch >= 1, h_pano_index, d_rot3 and d_img are required"};
-  const size_t npx = (size_t)H * W;
-  return gather_run(kind, launch_pano_rotate, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_rot3 != nullptr, H, W, d_img,
-                    !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr, misalign(d_up, 15) | misalign(d_lat, 15), stream,
-                    [=](PanoRotBatch& rb, int i0) {
-                      rb.inverse = inverse ? 1 : 0;
-                      rb.rot = d_rot3 + (size_t)i0 * 3;
-                      rb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
-                      rb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
-                    });
-}
-
-// The supersampled forms (gather_ss.hip): `samples` is checked first, then the parent's checks in the parent's order under the new name
 static bool samples_ok(const char* name, int samples) {
   if (samples >= 1 && samples <= PF_GATHER_MAX_SAMPLES) return true;
   g_create_error = fmt("%s: samples %d, must be in [1, %d]", name, samples, PF_GATHER_MAX_SAMPLES);
   return false;
 }
 
-int pf_pano_crop_ss(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
-                    const float* d_cam7, int H, int W, void* d_img, float* d_up, float* d_lat, int samples, void* stream) {
-  static const GatherKind kind{"pf_pano_crop_ss", "panorama", "crop", 2, "needs at least one panorama (h_pano, h_pano_hw)",
-                               "batch >= 1, h_pano_index, d_cam7 and d_img are required"};
-  if (!samples_ok(kind.name, samples)) return PF_ERR_ARG;
+// A gather and its supersampled form (gather_ss.hip) are one body under two names.  The batch type says which of the two runs: the form checks
+// `samples` first and sets it in its batch, the parent has neither; then the parent's checks in the parent's order under the entry point's name
+template <class Batch>
+static int pano_crop_run(const char* name, void (*launch)(const Batch&, int, hipStream_t), int samples, int device, int n_pano, const void* const* pano,
+                         const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index, const float* d_cam7, int H, int W, void* d_img, float* d_up,
+                         float* d_lat, void* stream) {
+  constexpr bool ss = std::is_same<Batch, PanoSsBatch>::value;
+  const GatherKind kind{name, "panorama", "crop", 2, "needs at least one panorama (h_pano, h_pano_hw)",
+                        "batch >= 1, h_pano_index, d_cam7 and d_img are required"};
+  if (ss && !samples_ok(name, samples)) return PF_ERR_ARG;
   const size_t npx = (size_t)H * W;
-  return gather_run(kind, launch_pano_crop_ss, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_cam7 != nullptr, H, W, d_img,
+  return gather_run(kind, launch, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_cam7 != nullptr, H, W, d_img,
                     !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr, misalign(d_up, 15) | misalign(d_lat, 15), stream,
-                    [=](PanoSsBatch& pb, int i0) {
-                      pb.samples = samples;
+                    [=](Batch& pb, int i0) {
+                      if constexpr (ss) pb.samples = samples;
                       pb.cam = d_cam7 + (size_t)i0 * 7;
                       pb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
                       pb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
                     });
 }
 
-int pf_reproject_ss(int device, int n_src, const void* const* src, const int32_t* src_hw, int dtype, int B, const int32_t* src_index,
-                    const float* d_cam_src7, const float* d_cam_dst7, int H, int W, float fill, void* d_img, uint8_t* d_valid, float* d_map, int samples,
-                    void* stream) {
-  static const GatherKind kind{"pf_reproject_ss", "source", "output", 1, "needs at least one source image (h_src, h_src_hw)",
-                               "batch >= 1, h_src_index, d_cam_src7, d_cam_dst7 and d_img are required"};
-  if (!samples_ok(kind.name, samples)) return PF_ERR_ARG;
+int pf_pano_crop(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
+                 const float* d_cam7, int H, int W, void* d_img, float* d_up, float* d_lat, void* stream) {
+  return pano_crop_run("pf_pano_crop", launch_pano_crop, 1, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_cam7, H, W, d_img, d_up, d_lat, stream);
+}
+
+int pf_pano_crop_ss(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
+                    const float* d_cam7, int H, int W, void* d_img, float* d_up, float* d_lat, int samples, void* stream) {
+  return pano_crop_run("pf_pano_crop_ss", launch_pano_crop_ss, samples, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_cam7, H, W, d_img, d_up,
+                       d_lat, stream);
+}
+
+template <class Batch>
+static int reproject_run(const char* name, void (*launch)(const Batch&, int, hipStream_t), int samples, int device, int n_src, const void* const* src,
+                         const int32_t* src_hw, int dtype, int B, const int32_t* src_index, const float* d_cam_src7, const float* d_cam_dst7, int H, int W,
+                         float fill, void* d_img, uint8_t* d_valid, float* d_map, void* stream) {
+  constexpr bool ss = std::is_same<Batch, ReprojSsBatch>::value;
+  const GatherKind kind{name, "source", "output", 1, "needs at least one source image (h_src, h_src_hw)",
+                        "batch >= 1, h_src_index, d_cam_src7, d_cam_dst7 and d_img are required"};
+  if (ss && !samples_ok(name, samples)) return PF_ERR_ARG;
   const size_t npx = (size_t)H * W;
-  return gather_run(kind, launch_reproject_ss, device, n_src, src, src_hw, dtype, B, src_index, d_cam_src7 && d_cam_dst7, H, W, d_img, nullptr,
-                    misalign(d_valid, 3) | misalign(d_map, 15), stream, [=](ReprojSsBatch& rb, int i0) {
-                      rb.samples = samples;
+  return gather_run(kind, launch, device, n_src, src, src_hw, dtype, B, src_index, d_cam_src7 && d_cam_dst7, H, W, d_img, nullptr,
+                    misalign(d_valid, 3) | misalign(d_map, 15), stream, [=](Batch& rb, int i0) {
+                      if constexpr (ss) rb.samples = samples;
                       rb.fill = fill;
                       rb.cam_src = d_cam_src7 + (size_t)i0 * 7;
                       rb.cam_dst = d_cam_dst7 + (size_t)i0 * 7;
@@ -156,21 +131,49 @@ int pf_reproject_ss(int device, int n_src, const void* const* src, const int32_t
                     });
 }
 
-int pf_pano_rotate_ss(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
-                      const float* d_rot3, int inverse, int H, int W, void* d_img, float* d_up, float* d_lat, int samples, void* stream) {
-  static const GatherKind kind{"pf_pano_rotate_ss", "panorama", "output", 2, "needs at least one panorama (h_pano, h_pano_hw)",
-                               "batch >= 1, h_pano_index, d_rot3 and d_img are required"};
-  if (!samples_ok(kind.name, samples)) return PF_ERR_ARG;
+int pf_reproject(int device, int n_src, const void* const* src, const int32_t* src_hw, int dtype, int B, const int32_t* src_index,
+                 const float* d_cam_src7, const float* d_cam_dst7, int H, int W, float fill, void* d_img, uint8_t* d_valid, float* d_map, void* stream) {
+  return reproject_run("pf_reproject", launch_reproject, 1, device, n_src, src, src_hw, dtype, B, src_index, d_cam_src7, d_cam_dst7, H, W, fill, d_img,
+                       d_valid, d_map, stream);
+}
+
+int pf_reproject_ss(int device, int n_src, const void* const* src, const int32_t* src_hw, int dtype, int B, const int32_t* src_index,
+                    const float* d_cam_src7, const float* d_cam_dst7, int H, int W, float fill, void* d_img, uint8_t* d_valid, float* d_map, int samples,
+                    void* stream) {
+  return reproject_run("pf_reproject_ss", launch_reproject_ss, samples, device, n_src, src, src_hw, dtype, B, src_index, d_cam_src7, d_cam_dst7, H, W, fill,
+                       d_img, d_valid, d_map, stream);
+}
+
+template <class Batch>
+static int pano_rotate_run(const char* name, void (*launch)(const Batch&, int, hipStream_t), int samples, int device, int n_pano, const void* const* pano,
+                           const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index, const float* d_rot3, int inverse, int H, int W, void* d_img,
+                           float* d_up, float* d_lat, void* stream) {
+  constexpr bool ss = std::is_same<Batch, PanoRotSsBatch>::value;
+  const GatherKind kind{name, "panorama", "output", 2, "needs at least one panorama (h_pano, h_pano_hw)",
+                        "batch >= 1, h_pano_index, d_rot3 and d_img are required"};
+  if (ss && !samples_ok(name, samples)) return PF_ERR_ARG;
   const size_t npx = (size_t)H * W;
-  return gather_run(kind, launch_pano_rotate_ss, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_rot3 != nullptr, H, W, d_img,
+  return gather_run(kind, launch, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_rot3 != nullptr, H, W, d_img,
                     !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr, misalign(d_up, 15) | misalign(d_lat, 15), stream,
-                    [=](PanoRotSsBatch& rb, int i0) {
-                      rb.samples = samples;
+                    [=](Batch& rb, int i0) {
+                      if constexpr (ss) rb.samples = samples;
                       rb.inverse = inverse ? 1 : 0;
                       rb.rot = d_rot3 + (size_t)i0 * 3;
                       rb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
                       rb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
                     });
+}
+
+int pf_pano_rotate(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
+                   const float* d_rot3, int inverse, int H, int W, void* d_img, float* d_up, float* d_lat, void* stream) {
+  return pano_rotate_run("pf_pano_rotate", launch_pano_rotate, 1, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_rot3, inverse, H, W, d_img, d_up,
+                         d_lat, stream);
+}
+
+int pf_pano_rotate_ss(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int B, const int32_t* pano_index,
+                      const float* d_rot3, int inverse, int H, int W, void* d_img, float* d_up, float* d_lat, int samples, void* stream) {
+  return pano_rotate_run("pf_pano_rotate_ss", launch_pano_rotate_ss, samples, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_rot3, inverse, H, W,
+                         d_img, d_up, d_lat, stream);
 }
 
 // Cube maps as the source (cube_gather.hip): `samples`, then that every cube is square, then gather_run's checks with the source size (N, N)

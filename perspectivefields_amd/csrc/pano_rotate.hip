@@ -40,17 +40,7 @@ struct RotConsts {
 __device__ __forceinline__ void rot_setup(const float* rot, int inverse, int H, int W, RotConsts* c) {
 #pragma clang fp contract(off)
   const float roll = rot[0], pitch = rot[1], yaw = rot[2];
-  float R[9], sy, cy, Q[9];
-  cam_rotation(roll, pitch, R);
-  sincosf(yaw, &sy, &cy);
-  // Y(yaw) R, Y = [[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]]
-  for (int k = 0; k < 3; ++k) {
-    Q[k] = fmaf(cy, R[k], sy * R[6 + k]);
-    Q[3 + k] = R[3 + k];
-    Q[6 + k] = fmaf(cy, R[6 + k], -(sy * R[k]));
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) c->A[3 * i + j] = inverse ? Q[3 * j + i] : Q[3 * i + j];
+  pano_rotation(rot, inverse, c->A);
   c->g[0] = -c->A[3]; c->g[1] = -c->A[4]; c->g[2] = -c->A[5];
   c->kx = (float)W * kInv2Pi;
   c->ky = (float)H * kInvPi;
