@@ -133,6 +133,22 @@ def test_public_names():
     assert callable(pkg.PerspectiveFields.field_errors)
 
 
+def test_every_public_name_resolves_to_one_object():
+    """every name of __all__ resolves lazily, is a function or a class (model_zoo: the table), and is the object that perspectivefields.py re-exports"""
+    from collections.abc import Mapping
+
+    import perspectivefields_amd as pkg
+    from perspectivefields_amd import perspectivefields as pfm
+
+    assert len(pkg.__all__) == len(set(pkg.__all__)) == 32
+    for name in pkg.__all__:
+        obj = getattr(pkg, name)
+        assert isinstance(obj, Mapping) if name == "model_zoo" else callable(obj), name
+        assert getattr(pfm, name) is obj, name
+    with pytest.raises(AttributeError):
+        pkg.no_such_name
+
+
 def test_field_errors_argument_errors_without_a_gpu():
     from perspectivefields_amd import FieldErrorAccumulator, field_errors
     from perspectivefields_amd.engine import PfError
