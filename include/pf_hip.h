@@ -604,8 +604,8 @@ int pf_cube_to_pano(int device, int n_cube, const void* const* h_cube, const int
  * Q = Y(yaw) R(roll, pitch) is the lens -> world rotation; F is in pixels per unit of rho; (Cx, Cy) is the centre of the image circle in pixel-edge
  * units of the frame; theta_max is the half field of view in radians, up to pi; band >= 0 is the feather width in radians.  The projection kind is
  * one integer per call: PF_FISHEYE_EQUIDISTANT rho(t) = t, PF_FISHEYE_EQUISOLID rho(t) = 2 sin(t / 2), PF_FISHEYE_STEREOGRAPHIC rho(t) = 2 tan(t / 2);
- * k1 ... k4 are the Kannala-Brandt polynomial (OpenCV's fisheye model is the equidistant kind with F = f).  Only the forward projection
- * (direction -> pixel) is used, so nothing is inverted on the device.
+ * k1 ... k4 are the Kannala-Brandt polynomial (OpenCV's fisheye model is the equidistant kind with F = f).  These two entry points use only the forward
+ * projection (direction -> pixel); the inverse is pf_pano_to_fisheye's, below.
  * The value of a frame in a unit world direction D, per lens l = 0, 1 in that order:
  *   1 angle     X = Ql^T D, h = hypot(X.x, X.y), theta = atan2(h, X.z)
  *   2 point     theta_d = theta (1 + theta^2 (k1 + theta^2 (k2 + theta^2 (k3 + theta^2 k4)))), Horner-wise as written; r = F rho(theta_d);
@@ -647,6 +647,52 @@ int pf_fisheye_to_pano(int device, int n_frame, const void* const* h_frame, cons
                        const int32_t* h_frame_index /*[batch]*/, const float* d_lens /*[batch][2][12]*/,
                        const float* d_rot3 /*[batch][3] roll, pitch, yaw, radians*/, int inverse, int H, int W, float fill,
                        void* d_img /*[batch][H][W][3], dtype*/, uint8_t* d_valid /*or NULL*/, int samples, void* stream);
+
+/* Fisheye and dual-fisheye frames as a TARGET: equirectangular panoramas -> the frames of one or two lenses, with the perspective fields of the
+ * fisheye camera (fisheye_target.hip).  Conventions and the 12-float lens row are those of pf_fisheye_crop above.
+ * An OUTPUT is an H x W frame (H, W >= 1) with its two lens rows d_lens[batch][2][12]; the projection kind is one integer per call; the source is an
+ * equirectangular panorama (Hp, Wp, 3), each side >= 2, in pf_pano_crop's longitude / latitude convention.
+ * PER LENS (lane 0): Q = Y(yaw) R(roll, pitch); R = R_pitch R_roll; g = R^T (0, -1, 0), world up in the lens' coordinates; the lens is ON exactly as
+ * above (its 12 entries finite and theta_max > 0); r_max = F rho(theta_d(theta_max)), the radius of its image circle, with theta_d and rho as above.
+ * THE INVERSE PROJECTION at the image point (a, b), pixel-edge units, lens l = 0 first, then lens 1:
+ *   1 radius    dx = a - Cx, dy = b - Cy, r = hypot(dx, dy)
+ *   2 owner     the lens OWNS the point iff it is on and r_max - r > 0: a positive comparison, a NaN owns nothing.  The first owner wins: there is
+ *               no blending in a target frame (`band` is not used).  fisheye_lens refuses a non-monotone r(theta), so r < r_max <=> theta <
+ *               theta_max, the coverage of the source side
+ *   3 theta_d   rho = r / F; theta_d = rho (equidistant) | 2 asin(min(rho / 2, 1)) (equisolid) | 2 atan(rho / 2) (stereographic)
+ *   4 theta     theta = theta_d if k1 = ... = k4 = 0.  Otherwise from theta_0 = min(theta_d, theta_max) exactly PF_FISHEYE_NEWTON_STEPS = 10 steps
+ *               theta <- clamp(theta - (P(theta) - theta_d) / P'(theta), 0, theta_max), with P(t) = t (1 + t^2 (k1 + t^2 (k2 + t^2 (k3 + t^2 k4))))
+ *               Horner-wise as above and P'(t) = 1 + t^2 (3 k1 + t^2 (5 k2 + t^2 (7 k3 + 9 k4 t^2))): a fixed count, no data-dependent exit
+ *   5 direction (c, s) = (dx, dy) / r, (1, 0) where r = 0; X = (sin theta c, sin theta s, cos theta) in the lens' coordinates
+ * THE IMAGE: D = Q X; pf_pano_crop's sphere and panorama lines: lat = -atan2(D.y, hypot(D.x, D.z)), lon = atan2(D.x, D.z), u = (lon / 2 pi + 1/2) Wp
+ * - 1/2, v = (1/2 - lat / pi) Hp - 1/2; the bilinear sample of the panorama gathers at (u, v) (columns wrap, rows clamp).  A point no lens owns has
+ * no value.  `samples` = S in 1 ... PF_GATHER_MAX_SAMPLES under the rule of the supersampled gathers: a pixel is the mean of the valid ones of its
+ * S x S sub-samples at (col + (j + 1/2)/S, row + (i + 1/2)/S), `fill` without one; the mask is 1 iff a sub-sample is valid.  PF_PANO_U8: the fp32
+ * value rounded half up, clamped to [0, 255].  A lens row with a non-finite entry owns nothing and issues no load.
+ * THE LABELS (the perspective fields of the fisheye camera) are taken at the pixel centre (col + 1/2, row + 1/2), whatever `samples`, and use R, not
+ * Q: the yaw does not enter them, nor their bits.
+ *   latitude    degrees: -atan2(W.y, hypot(W.x, W.z)) with W = R X
+ *   up          the image direction of a step along world up.  t = g - (g . X) X; e_theta = (cos theta c, cos theta s, -sin theta), e_phi = (-s, c, 0)
+ *               (t = (t . e_theta) e_theta + (t . e_phi) e_phi, and t . e = g . e for both); m = rho(theta_d) = r / F, m' = rho'(theta_d) P'(theta)
+ *               with rho' = 1 | cos(theta_d / 2) | 1 / cos^2(theta_d / 2);
+ *               up ~ m' (t . e_theta) (c, s) + (m / sin theta) (t . e_phi) (-s, c), normalised; at r = 0, m / sin theta is replaced by m'.
+ *               Where |t|^2 < PF_PANO_UP_MIN_T2 (the pixel looks at the zenith or the nadir) up = NaN and the latitude stays.
+ *   A pixel without an owner has NaN in all three planes.
+ * pf_pano_to_fisheye: h_pano / h_pano_hw / h_pano_index as in pf_pano_crop; d_img = DEVICE [batch][H][W][3] of `dtype`; d_valid = NULL or DEVICE
+ * [batch][H][W] bytes; d_up [batch][2][H][W] and d_lat [batch][H][W] fp32: both or neither (NULL: no labels).  pf_fisheye_fields: the labels alone,
+ * no source; its bits are those of pf_pano_to_fisheye's labels.  The 4-pixel vector stores are taken when W % 4 == 0 and d_img (4 bytes uint8, 16
+ * bytes fp32), d_valid (4 bytes), d_up and d_lat (16 bytes) are aligned; otherwise scalar stores give the same bits.  Argument errors return
+ * PF_ERR_ARG before any device work with a message that begins with the function's name, checked in this order: `samples` out of range; an unknown
+ * `kind`; then n_pano < 1 or NULL source lists, a bad dtype, a NULL panorama or a panorama side < 2, batch < 1 or a NULL required pointer
+ * (h_pano_index, d_lens, d_img), H or W < 1, one of d_up / d_lat without the other, an index out of range.  One launch per 32 outputs on `stream`,
+ * no workspace, no host synchronisation; stateless, no handle; deterministic, each output's bits independent of the batch it is in. */
+#define PF_FISHEYE_NEWTON_STEPS 10
+int pf_pano_to_fisheye(int device, int n_pano, const void* const* h_pano, const int32_t* h_pano_hw /*[n_pano][2]*/, int dtype /*PF_PANO_U8|PF_PANO_F32*/,
+                       int kind /*PF_FISHEYE_...*/, int batch, const int32_t* h_pano_index /*[batch]*/, const float* d_lens /*[batch][2][12]*/, int H, int W,
+                       float fill, void* d_img /*[batch][H][W][3], dtype*/, uint8_t* d_valid /*or NULL*/, float* d_up /*[batch][2][H][W] or NULL*/,
+                       float* d_lat /*[batch][H][W], with d_up*/, int samples, void* stream);
+int pf_fisheye_fields(int device, int kind, int batch, const float* d_lens /*[batch][2][12]*/, int H, int W, float* d_up /*[batch][2][H][W]*/,
+                      float* d_lat /*[batch][H][W]*/, void* stream);
 
 /* The relative yaw of camera views of one centre, from the pictures: for ordered pairs (a, b) of views and a list of candidate turns, the moments of
  * the two luminance images on their overlap, from which the zero-mean normalised cross-correlation follows (yaw_align.hip).

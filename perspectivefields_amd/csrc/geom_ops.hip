@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip, fisheye_gather.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the pasting of objects (composite.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip, fisheye_gather.hip, fisheye_target.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the pasting of objects (composite.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include <type_traits>
 
 #include "host_pack.h"
@@ -252,6 +252,54 @@ int pf_fisheye_to_pano(int device, int n_frame, const void* const* frame, const 
                       fb.rot = d_rot3 + (size_t)i0 * 3;
                       fb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
                     });
+}
+
+// Fisheye frames as the target (fisheye_target.hip): `samples`, then the projection kind, then gather_run's checks with the panoramas as the sources
+int pf_pano_to_fisheye(int device, int n_pano, const void* const* pano, const int32_t* pano_hw, int dtype, int kind, int B, const int32_t* pano_index,
+                       const float* d_lens, int H, int W, float fill, void* d_img, uint8_t* d_valid, float* d_up, float* d_lat, int samples, void* stream) {
+  static const GatherKind gk{"pf_pano_to_fisheye", "panorama", "frame", 2, "needs at least one panorama (h_pano, h_pano_hw)",
+                             "batch >= 1, h_pano_index, d_lens and d_img are required"};
+  if (!samples_ok(gk.name, samples) || !fisheye_kind_ok(gk.name, kind)) return PF_ERR_ARG;
+  const size_t npx = (size_t)H * W;
+  return gather_run(gk, launch_pano_to_fisheye, device, n_pano, pano, pano_hw, dtype, B, pano_index, d_lens != nullptr, H, W, d_img,
+                    !d_up != !d_lat ? "d_up and d_lat are both given or both NULL" : nullptr,
+                    misalign(d_valid, 3) | misalign(d_up, 15) | misalign(d_lat, 15), stream, [=](PanoToFisheyeBatch& fb, int i0) {
+                      fb.samples = samples;
+                      fb.kind = kind;
+                      fb.fill = fill;
+                      fb.lens = d_lens + (size_t)i0 * PF_FISHEYE_MAX_LENSES * PF_FISHEYE_LENS_FLOATS;
+                      fb.valid = d_valid ? d_valid + (size_t)i0 * npx : nullptr;
+                      fb.up = d_up ? d_up + (size_t)i0 * 2 * npx : nullptr;
+                      fb.lat = d_lat ? d_lat + (size_t)i0 * npx : nullptr;
+                    });
+}
+
+// the labels of pf_pano_to_fisheye without a source: the projection kind, then its checks that concern the outputs, its tile and its launch groups
+int pf_fisheye_fields(int device, int kind, int B, const float* d_lens, int H, int W, float* d_up, float* d_lat, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_fisheye_fields: " + m; return PF_ERR_ARG; };
+  if (!fisheye_kind_ok("pf_fisheye_fields", kind)) return PF_ERR_ARG;
+  if (B < 1 || !d_lens || !d_up || !d_lat) return bad("batch >= 1, d_lens, d_up and d_lat are required");
+  if (H < 1 || W < 1) return bad(fmt("output size %d x %d", H, W));
+  const int tpr = 16;  // a 64 x 16 pixel tile, as the gathers
+  const long tiles_x = (W + 4 * tpr - 1) / (4 * tpr), tiles_y = (H + 256 / tpr - 1) / (256 / tpr);
+  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("output size %d x %d too large", H, W));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  const size_t npx = (size_t)H * W;
+  const int vec = (W % 4 == 0 && (misalign(d_up, 15) | misalign(d_lat, 15)) == 0) ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i0 = 0; i0 < B; i0 += FisheyeFieldsBatch::MAX) {
+    FisheyeFieldsBatch fb;
+    fb.d = GatherDims{std::min(B - i0, (int)FisheyeFieldsBatch::MAX), H, W, tpr, (int)tiles_x, (int)tiles_y, vec};
+    fb.kind = kind;
+    fb.lens = d_lens + (size_t)i0 * PF_FISHEYE_MAX_LENSES * PF_FISHEYE_LENS_FLOATS;
+    fb.up = d_up + (size_t)i0 * 2 * npx;
+    fb.lat = d_lat + (size_t)i0 * npx;
+    launch_fisheye_fields(fb, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_fisheye_fields: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
 }
 
 // the labels of pf_pano_rotate without a source: its checks that concern the outputs, its tile and its launch groups

@@ -608,6 +608,36 @@ void launch_fisheye_to_pano(const FisheyePanoBatch& fb, int dtype, hipStream_t s
 static_assert(offsetof(FisheyeCropBatch, samples) == 28 && offsetof(FisheyeCropBatch, src) == 32, "FisheyeCropBatch layout");
 static_assert(offsetof(FisheyePanoBatch, samples) == 28 && offsetof(FisheyePanoBatch, src) == 32, "FisheyePanoBatch layout");
 
+// equirectangular panoramas -> fisheye and dual-fisheye frames + the perspective fields of the fisheye camera (fisheye_target.hip, include/pf_hip.h
+// pf_pano_to_fisheye / pf_fisheye_fields): the outputs are frames (H, W, 3), each with its PF_FISHEYE_MAX_LENSES lens rows; `samples` as in the
+// supersampled gathers
+struct PanoToFisheyeBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int samples;        // S in [1, PF_GATHER_MAX_SAMPLES]
+  GatherSources src;  // the panoramas (Hp, Wp, 3)
+  int kind;           // PF_FISHEYE_EQUIDISTANT | PF_FISHEYE_EQUISOLID | PF_FISHEYE_STEREOGRAPHIC
+  float fill;         // value of a pixel that no lens owns
+  const float* lens;  // [n][PF_FISHEYE_MAX_LENSES][PF_FISHEYE_LENS_FLOATS]
+  void* img;          // [n][H][W][3], the panoramas' type
+  uint8_t* valid;     // NULL or [n][H][W]: 1 where a sub-sample has an owner
+  float* up;          // NULL (no labels) or [n][2][H][W]
+  float* lat;         // NULL or [n][H][W] degrees
+};
+void launch_pano_to_fisheye(const PanoToFisheyeBatch& fb, int dtype, hipStream_t s);
+// the labels alone (pf_fisheye_fields): no source
+struct FisheyeFieldsBatch {
+  static constexpr int MAX = GatherSources::MAX;
+  GatherDims d;
+  int kind;
+  const float* lens;  // [n][PF_FISHEYE_MAX_LENSES][PF_FISHEYE_LENS_FLOATS]
+  float* up;          // [n][2][H][W]
+  float* lat;         // [n][H][W] degrees
+};
+void launch_fisheye_fields(const FisheyeFieldsBatch& fb, hipStream_t s);
+static_assert(offsetof(PanoToFisheyeBatch, samples) == 28 && offsetof(PanoToFisheyeBatch, src) == 32, "PanoToFisheyeBatch layout");
+static_assert(offsetof(FisheyeFieldsBatch, kind) == 28 && offsetof(FisheyeFieldsBatch, lens) == 32, "FisheyeFieldsBatch layout");
+
 // camera views of one centre -> equirectangular panoramas (pano_compose.hip, include/pf_hip.h pf_pano_compose): the outputs of a launch are up to MAX
 // panoramas, its sources up to MAX views; panorama k blends the views [first[k], first[k] + count[k]) of the launch in that order
 struct ComposeBatch {

@@ -449,6 +449,14 @@ def _fisheye_frames(fn, frames):
     return _sources(fn, frames, ("frame", "frames"), "a frame must be (Hs, Ws, 3) with Hs, Ws >= 1", 1)
 
 
+def _fisheye_per_frame(lenses):
+    """whether `lenses` holds one entry per frame (an array (n, 1 or 2, 12) or a list of 2-d entries) and not one entry shared by every frame"""
+    ndim = lambda e: e.dim() if torch.is_tensor(e) else np.ndim(e)
+    if isinstance(lenses, (list, tuple)):
+        return len(lenses) > 0 and all(ndim(e) == 2 for e in lenses)
+    return ndim(lenses) == 3
+
+
 def _fisheye_lens_table(fn, lenses, n_frame):
     """`lenses` -> (n_frame, 2, 12) float64.  Anything 1-d or 2-d is ONE entry shared by every frame: a row (12,), or 1 or 2 rows ((1, 12), (2, 12),
     also as a list of two rows, so two rows are always the two lenses of a frame, never one lens each for two frames).  Per frame: an array
@@ -465,12 +473,7 @@ def _fisheye_lens_table(fn, lenses, n_frame):
             raise ValueError(f"{fn}: a frame's lenses are one row of {FISHEYE_LENS_FLOATS} values or {FISHEYE_MAX_LENSES} such rows; got shape {tuple(a.shape)}")
         return np.concatenate([a, np.zeros((FISHEYE_MAX_LENSES - a.shape[0], FISHEYE_LENS_FLOATS))])
 
-    ndim = lambda e: e.dim() if torch.is_tensor(e) else np.ndim(e)
-    if isinstance(lenses, (list, tuple)):
-        per_frame = len(lenses) > 0 and all(ndim(e) == 2 for e in lenses)
-    else:
-        per_frame = ndim(lenses) == 3
-    if not per_frame:
+    if not _fisheye_per_frame(lenses):
         return np.repeat(entry(lenses)[None], n_frame, axis=0)
     if len(lenses) != n_frame:
         raise ValueError(f"{fn}: lenses has {len(lenses)} entries for {n_frame} frames")
@@ -551,6 +554,87 @@ def fisheye_to_panorama(frames, lenses, *, height, width, roll=0.0, pitch=0.0, y
     if return_mask:
         out += (valid.view(torch.bool),)
     return out[0] if len(out) == 1 else out
+
+
+def _cuda_device(fn, device, ts=()):
+    """the CUDA device of a call without a source: `device`, else that of a tensor argument, else the current one, with its index"""
+    if device is None:
+        device = next((t.device for t in ts if torch.is_tensor(t) and t.is_cuda), None)
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise PfError(f"{fn} runs on the GPU only (no CPU path)")
+    if not torch.cuda.is_available():
+        raise PfError(f"{fn} runs on the GPU only and no GPU is available")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def panorama_to_fisheye(pano, lenses, *, height, width, projection="equidistant", pano_index=None, fill=0, return_mask=False, fields=False, samples=1):
+    """Equirectangular panoramas -> fisheye and dual-fisheye frames on the GPU, with the ground-truth perspective fields of the fisheye camera on
+    request: `crop_panorama` for a real fisheye lens (labelled fisheye data out of panoramas), and the way back from `fisheye_to_panorama` /
+    `crop_fisheye`.  Lens model, inverse projection and labels: include/pf_hip.h pf_pano_to_fisheye.
+
+    pano: a CUDA tensor (Hp, Wp, 3), uint8 or float32, or a list of them (one dtype, one device).  lenses: as `crop_fisheye`, with the outputs in
+    the place of the frames: a row of `fisheye_lens`, a pair of rows (`dual_fisheye_lenses(height, width, fov)` gives the side-by-side frame), both
+    shared by every output, or one such entry per output; the rows hold radians and are read on the host.  A pixel belongs to the first lens whose
+    image circle holds it: a target frame is not blended and `band` is not used.  projection: the kind of every lens of the call.
+    height, width: the size of every frame.  The number of outputs B is that of pano_index (B integers, the panorama of each output), else that of
+    per-output lenses, else one output per panorama; without pano_index output i reads panorama i, or panorama 0 when there is one panorama.
+    fill: the value of the pixels outside every image circle.  samples=S (1 .. 4) antialiases a frame that minifies its panorama, as in
+    `crop_panorama`; the fields do not depend on it.
+    Returns the images (B, H, W, 3) in the panorama's dtype; with fields=True (images, up (B, 2, H, W), lat (B, H, W) degrees), which are
+    `fisheye_fields` of the same lenses bit for bit: NaN outside every image circle, up NaN at a pixel centre on the zenith or nadir; with
+    return_mask=True the mask (B, H, W) bool comes last: False where no lens owns the pixel, which then holds `fill`.
+    GPU only: CPU panoramas raise PfError."""
+    fn = "panorama_to_fisheye"
+    samples = _check_samples(fn, samples)
+    kind = _fisheye_kind(fn, projection)
+    _, n, sizes, dev, make = _sources(fn, pano, ("panorama", "panoramas"), "a panorama must be (Hp, Wp, 3) with Hp, Wp >= 2", 2)
+    H, W = _out_size(height, width, "frame size")
+    fill = float(fill)
+    if pano_index is not None:
+        B = len(pano_index)
+    elif _fisheye_per_frame(lenses):
+        B = len(lenses)
+    else:
+        B = n
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one output")
+    if pano_index is None and n > 1 and B != n:
+        raise ValueError(f"{fn}: {B} outputs of {n} panoramas, so pano_index is required")
+    idx = _source_index("pano_index", list(range(B)) if pano_index is None and n > 1 else pano_index, B, n, "outputs")
+    table = _fisheye_lens_table(fn, lenses, B)
+    lens = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32)).to(dev)
+    panos = make()
+    img, up, lat = _image_and_fields(B, H, W, panos[0].dtype, dev, fields)
+    valid = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_mask else None
+    head, c_idx = _source_args(dev, panos, sizes, idx)
+    _launch("pf_pano_to_fisheye", dev, head + (kind, B, c_idx, lens.data_ptr(), H, W, fill, img.data_ptr(), _ptr(valid), _ptr(up), _ptr(lat), samples))
+    out = (img,) + ((up, lat) if fields else ()) + ((valid.view(torch.bool),) if return_mask else ())
+    return out[0] if len(out) == 1 else out
+
+
+def fisheye_fields(lenses, *, height, width, projection="equidistant", device=None):
+    """The perspective fields of a fisheye or dual-fisheye camera on the GPU: the counterpart of `fields_from_params` for a calibrated fisheye lens
+    (OpenCV `fisheye` K and D, or a maker's equidistant, equisolid or stereographic lens) with a known roll and pitch, and the labels of
+    `panorama_to_fisheye(..., fields=True)` for the same lenses, bit for bit (the yaw of a lens does not enter).  Model: include/pf_hip.h
+    pf_fisheye_fields.
+    lenses: a row of `fisheye_lens`, a pair of rows (one frame), or one such entry per frame (B frames); height, width: the size of the frames.
+    Returns (up (B, 2, H, W) unit vectors, latitude (B, H, W) degrees) in the layout of pred_gravity_original / pred_latitude_original: what
+    `field_errors` and `draw_perspective_fields` take.  Both are NaN outside every image circle; up is NaN at a pixel centre on the zenith or
+    nadir.  device: a CUDA device, default that of a tensor argument, else the current one."""
+    fn = "fisheye_fields"
+    kind = _fisheye_kind(fn, projection)
+    H, W = _out_size(height, width, "field size")
+    B = len(lenses) if _fisheye_per_frame(lenses) else 1
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one frame")
+    table = _fisheye_lens_table(fn, lenses, B)
+    dev = _cuda_device(fn, device, lenses if isinstance(lenses, (list, tuple)) else (lenses,))
+    lens = torch.from_numpy(np.ascontiguousarray(table, dtype=np.float32)).to(dev)
+    up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+    lat = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    _launch("pf_fisheye_fields", dev, (dev.index, kind, B, lens.data_ptr(), H, W, up.data_ptr(), lat.data_ptr()))
+    return up, lat
 
 
 def panorama_to_cubemap(pano, size, *, roll=0.0, pitch=0.0, yaw=0.0, samples=1):

@@ -38,8 +38,8 @@ from .field_metrics import _FERR_BINS, _FERR_BINS_PER_DEG, _FERR_COLS, _FERR_SUM
 from .fields import fields_from_params, general_vfov_to_focal  # noqa: F401
 from .gathers import (BLEND_FEATHER, BLEND_MEAN, FISHEYE_LENS_FLOATS, FISHEYE_MAX_LENSES, FISHEYE_PROJECTIONS, GATHER_MAX_SAMPLES, PANO_F32, PANO_U8,  # noqa: F401
                       _COMPOSE_MAX_VIEWS, _check_samples, _cuda_image_list, _fisheye_lens_table, compose_panorama, crop_cubemap, crop_fisheye, crop_panorama,
-                      cubemap_face_cameras, cubemap_from_image, cubemap_to_image, cubemap_to_panorama, dual_fisheye_lenses, fisheye_lens, fisheye_to_panorama,
-                      panorama_fields, panorama_to_cubemap, reproject_image, rotate_panorama)
+                      cubemap_face_cameras, cubemap_from_image, cubemap_to_image, cubemap_to_panorama, dual_fisheye_lenses, fisheye_fields, fisheye_lens, fisheye_to_panorama,
+                      panorama_fields, panorama_to_cubemap, panorama_to_fisheye, reproject_image, rotate_panorama)
 from .placement import COMPOSITE_HARD, COMPOSITE_SOFT, composite_objects, placement_scores, placement_search, transform_fields  # noqa: F401
 from .yaw import _YAW_MAX_CAND, align_yaw, gravity_from_views, yaw_scores, yaw_tree  # noqa: F401
 
