@@ -13,12 +13,12 @@ CSRC = os.path.join(HERE, "csrc")
 # be prebuilt in the tree and travel to the GPU box together.
 # PF_LIB_SUFFIX=<s> (with PF_SKIP_DIGEST_CHECK=1) selects lib<s>/: a library built from OTHER sources kept next to the product for a same-box A/B.
 # PF_ASAN=1: lib_asan/ -- the HOST code of every translation unit under AddressSanitizer + UndefinedBehaviorSanitizer (device code unchanged), for the host-side
-# orchestration of engine.hip (stack allocator, checkpoint / tile-table parsers, weight repack): driven on CPU through pf_create(PF_DEVICE_NONE) by tests/test_host_asan.py
+# orchestration of the engine units (engine.hip, engine_weights.hip, engine_forward.hip: stack allocator, checkpoint / tile-table parsers, weight repack): driven on CPU through pf_create(PF_DEVICE_NONE) by tests/test_host_asan.py
 ASAN = os.environ.get("PF_ASAN", "0") == "1"
 _VARIANT = ("_tune" if os.environ.get("PF_TUNING_BUILD", "0") == "1" else "") + ("_asan" if ASAN else "") + os.environ.get("PF_LIB_SUFFIX", "")
 LIBDIR = os.path.join(HERE, "lib" + _VARIANT)
 LIB = os.path.join(LIBDIR, "libpf_hip.so")
-SOURCES = ["igemm.hip", "igemm_sb.hip", "igemm_sbf.hip", "igemm_sbh.hip", "wino.hip", "attn.hip", "attn_block.hip", "stem7.hip", "thin_linear.hip", "elem.hip", "dw7.hip", "dw7_pk.hip", "cnx_mlp.hip", "mit_mlp.hip", "rb_gemm.hip", "rb_chain.hip", "cnx_rb.hip", "fit_camera.hip", "fit_camera_usm.hip", "pano_crop.hip", "reproject.hip", "pano_compose.hip", "pano_rotate.hip", "gather_ss.hip", "cube_gather.hip", "fisheye_gather.hip", "fisheye_target.hip", "yaw_align.hip", "place_score.hip", "field_xform.hip", "draw_fields.hip", "composite.hip", "field_err.hip", "engine.hip", "engine_ops.hip", "geom_ops.hip"]
+SOURCES = ["igemm.hip", "igemm_sb.hip", "igemm_sbf.hip", "igemm_sbh.hip", "wino.hip", "attn.hip", "attn_block.hip", "stem7.hip", "thin_linear.hip", "elem.hip", "dw7.hip", "dw7_pk.hip", "cnx_mlp.hip", "mit_mlp.hip", "rb_gemm.hip", "rb_chain.hip", "cnx_rb.hip", "fit_camera.hip", "fit_camera_usm.hip", "pano_crop.hip", "reproject.hip", "pano_compose.hip", "pano_rotate.hip", "gather_ss.hip", "cube_gather.hip", "fisheye_gather.hip", "fisheye_target.hip", "yaw_align.hip", "place_score.hip", "field_xform.hip", "draw_fields.hip", "composite.hip", "field_err.hip", "engine.hip", "engine_weights.hip", "engine_forward.hip", "engine_ops.hip", "geom_ops.hip"]
 # dw7.hip: the scalar one-channel-per-lane kernel must not be SLP-vectorised (see the file header)
 # NO_PK_F32_FLAGS: these units are compiled without the packed-fp32 feature (pf_kernels.h PF_NO_PK_F32 says why); the x86 host pass prints an "ignoring feature"
 # line per function for it, filtered below

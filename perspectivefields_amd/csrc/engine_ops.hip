@@ -1,5 +1,5 @@
 // Op-level entry points of libpf_hip.so (pf_op_*: one kernel family each, host weights uploaded per call) -- what tests/test_gpu_ops.py and the tuning scripts call.
-// Not part of the inference path (the engine, engine.hip, never goes through here).
+// Not part of the inference path (the engine's forward, engine_forward.hip, never goes through here).
 #include "host_pack.h"
 
 using namespace pf;

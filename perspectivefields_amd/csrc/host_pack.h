@@ -1,4 +1,4 @@
-// Host-side helpers shared by the engine (engine.hip) and the op-level test / bench entry points (engine_ops.hip): error text, device check, the weight packers
+// Host-side helpers shared by the engine (engine.h and its units engine.hip, engine_weights.hip, engine_forward.hip) and the op-level test / bench entry points (engine_ops.hip): error text, device check, the weight packers
 // (conv layout, split planes, fused-MLP / row-block weight streams) and the temporary-upload helper of the op entry points.  Header-only (inline).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -301,7 +301,7 @@ void launch_nearest_nhwc4(const float* x, float* y, int B, int H, int W, int Ho,
 
 // ConvNeXt tail: global average pool -> LN(C) -> Linear(C->nout); out [B][nout]
 // Fused ConvNeXt block MLP (cnx_mlp.hip): y += ls * pwconv2(GELU(pwconv1(LayerNorm(d)))) for C = 96 / 192, hidden map in registers only.
-// wpk / tab: packed by cnx_mlp_pack (engine.hip)
+// wpk / tab: packed by cnx_mlp_pack (host_pack.h)
 bool cnx_mlp_supported(int C);
 bool cnx_mlp_preferred(int C);  // the stages where the engine uses it
 void launch_cnx_mlp(const float* d, float* y, const unsigned short* wpk, const float* tab, long M, int C, float eps, hipStream_t s, unsigned* sat = nullptr, float sat_limit = 65504.f);
@@ -324,7 +324,7 @@ bool cnx_rb_supported(int C);
 int cnx_rb_rows(int C);      // rows per block
 void launch_cnx_rb(const CnxRbArgs& a, int C, hipStream_t s);
 // Fused MiT block Mlp (mit_mlp.hip): y = x + fc2(GELU(dwconv3x3(fc1(LayerNorm(x))))) for C = 64 / 128; x and y are different buffers.
-// wpk / tab2: packed by mit_mlp_pack (engine.hip), one chunk of mit_mlp_chunk_bytes(C) per 32 hidden units
+// wpk / tab2: packed by mit_mlp_pack (host_pack.h), one chunk of mit_mlp_chunk_bytes(C) per 32 hidden units
 bool mit_mlp_supported(int C);
 bool mit_mlp_preferred(int C, int with128);  // the stages for which the engine builds its weights (with128 = Engine::mit_mlp128: smallest batch that takes the C = 128 form, 0 = never)
 int mit_mlp_chunk_bytes(int C);

@@ -1,5 +1,5 @@
-"""Which kernels the engine launches, on which streams, out of which scratch, is decided per forward from the batch size and the PF_* switches (engine.hip: pf_create,
-mit(), conv_g).  The op tests check every kernel against an fp64 reference; this file checks the DECISION: every switch at the batches where the paths it switches
+"""Which kernels the engine launches, on which streams, out of which scratch, is decided per forward from the batch size and the PF_* switches (engine.hip: pf_create;
+engine_forward.hip: mit(), conv_g).  The op tests check every kernel against an fp64 reference; this file checks the DECISION: every switch at the batches where the paths it switches
 are live, with the dispatch report (Engine.last_dispatch) as the witness that the switch acted at all.
 
 Every cell is a configuration a user can select.  Inputs are 320 x 320 uint8 images with a distinct seed per batch slot: identical images in both halves of a batch

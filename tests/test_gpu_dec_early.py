@@ -1,4 +1,4 @@
-"""The early decoder start (PF_DEC_EARLY, engine.hip dec_early_issue()): at decoder levels 0-2 the folded first conv fold[k] reads only the MiT stage output c_{k+1}
+"""The early decoder start (PF_DEC_EARLY, engine_forward.hip dec_early_issue()): at decoder levels 0-2 the folded first conv fold[k] reads only the MiT stage output c_{k+1}
 and r1c1[k] only fold[k]'s output, so they are issued on a side stream right after the stage-3 norm, beside MiT stage 4 and decoder levels 3 / 2.  The same kernels
 run with the same tiles on the same inputs: every comparison in this file is torch.equal, no tolerance.  The dispatch report (dec_early_taken) is the witness that
 the path ran -- or, under each of its gates, did not.

@@ -215,7 +215,7 @@ def test_sharded_product_class_on_one_gpu():
 
 
 def test_stage3_batch_split_is_bit_identical(monkeypatch):
-    """PF_S3_SPLIT (engine.hip mit(), "the stage-3 split"): MiT stage 3 (mix_transformers.py:198-202, 18 blocks) walks the batch as two half-batches on two streams.
+    """PF_S3_SPLIT (engine_forward.hip mit(), "the stage-3 split"): MiT stage 3 (mix_transformers.py:198-202, 18 blocks) walks the batch as two half-batches on two streams.
     Same kernels on the same images -- every output of a batch-32 forward must be bit-identical to the one-stream walk, with the deferred ParamNet branch beside it too."""
     from perspectivefields_amd import PerspectiveFields
 

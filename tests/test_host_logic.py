@@ -116,7 +116,7 @@ def test_product_never_imports_oracle():
 
 def test_fold_linear_into_conv_algebra():
     """The engine folds Linear(C->768) + zero-padded conv3x3(768->256) into one conv3x3(C->256) with a 9-case
-    bias table (csrc/engine.hip make_folded).  Same algebra in numpy, checked against the two-step form."""
+    bias table (csrc/engine_weights.hip make_folded).  Same algebra in numpy, checked against the two-step form."""
     g = torch.Generator().manual_seed(0)
     C, E, O, H, W = 8, 24, 6, 5, 7
     x = torch.randn(2, C, H, W, generator=g, dtype=torch.float64)
