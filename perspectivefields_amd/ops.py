@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import threading
 
 import numpy as np
 
@@ -41,6 +42,151 @@ def saturation_watch(limit=65504.0):
         lib.pf_op_set_saturation_watch(None, 0.0)
 
 
+# ---- checked outputs: every tensor a pf_op_* launch writes is allocated by _out(); inside checked_outputs() it is poisoned and guard-banded
+GUARD_BYTES = 256 * 1024      # on each side of an output: four full 64 KB output tiles (256 x 64 or 128 x 128 fp32, the largest of the tile table); a multiple of 512, so the
+                              # output keeps the alignment torch gives the backing buffer
+POISON_BYTE = 0xFF            # 0xFFFFFFFF, 0xFFFF: a NaN in fp32, fp16 and bf16 -- an element no kernel wrote fails every comparison downstream
+HOLD_LIMIT_BYTES = 1 << 30    # backing buffers a manager keeps before it verifies and releases them early
+_checked = threading.local()
+
+
+def guard_pattern(device):
+    """The GUARD_BYTES bytes every guard band holds: byte i = (131 i + 7) mod 256.  Not a constant, so a kernel that stores zeros, the poison or any one value into a
+    guard changes it."""
+    import torch
+
+    return ((torch.arange(GUARD_BYTES, dtype=torch.int64) * 131 + 7) & 0xFF).to(torch.uint8).to(device)
+
+
+class _Guarded:
+    """one output of _out() under checked_outputs(): `backing` = front guard | `nbytes` output bytes | back guard, all uint8"""
+
+    def __init__(self, label, backing, nbytes):
+        self.label, self.backing, self.nbytes = label, backing, nbytes
+
+    def guards(self):
+        """(2, GUARD_BYTES) view: row 0 the front guard, row 1 the back guard"""
+        return self.backing.as_strided((2, GUARD_BYTES), (GUARD_BYTES + self.nbytes, 1))
+
+    def body(self):
+        return self.backing[GUARD_BYTES:GUARD_BYTES + self.nbytes]
+
+
+class CheckedOutputs:
+    """What checked_outputs() yields.  `buffers`: the outputs allocated so far and not yet verified (a _Guarded each, in order)."""
+
+    def __init__(self):
+        self.buffers = []
+        self.held_bytes = 0
+        self.outputs = 0          # allocated since the block was entered
+        self._patterns = {}
+
+    def _pattern(self, device):
+        if device not in self._patterns:
+            self._patterns[device] = guard_pattern(device)
+        return self._patterns[device]
+
+    def allocate(self, shape, dtype, device, label, fill, poison):
+        import torch
+
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        shape = (int(shape),) if isinstance(shape, (int, np.integer)) else tuple(int(v) for v in shape)
+        nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty(0, dtype=dtype).element_size()
+        if self.held_bytes + nbytes + 2 * GUARD_BYTES > HOLD_LIMIT_BYTES and self.buffers:
+            self.verify()         # releases what was held: from here on the allocator may hand those blocks out again (poisoned afresh, guards rewritten)
+        g = _Guarded(label, torch.empty(nbytes + 2 * GUARD_BYTES, dtype=torch.uint8, device=device), nbytes)
+        g.guards().copy_(self._pattern(device))
+        out = g.body().view(dtype).view(shape)
+        if poison:
+            g.body().fill_(POISON_BYTE)
+        elif fill is not None:
+            out.fill_(fill)
+        self.buffers.append(g)
+        self.held_bytes += nbytes + 2 * GUARD_BYTES
+        self.outputs += 1
+        return out
+
+    def verify(self, release=True):
+        """Compares every guard held with the pattern (one device-to-host copy, which synchronises the current stream, for all of them) and lets the buffers go
+        (release=False: keeps them, for a caller that launches into the same buffers again).  Raises AssertionError on damage: for each damaged guard the op's label,
+        the side, the damaged byte count and the offset of the first damaged byte from the output's first byte (negative in the front guard, >= the output's size in
+        the back guard)."""
+        import torch
+
+        held = list(self.buffers)
+        if release:
+            self.buffers, self.held_bytes = [], 0
+        if not held:
+            return
+        bad = torch.stack([g.guards().ne(self._pattern(g.backing.device)).sum(1) for g in held]).cpu()
+        if not bool(bad.any()):
+            return
+        msgs = []
+        for g, row in zip(held, bad.tolist()):
+            for side, count in enumerate(row):
+                if count:
+                    first = int(g.guards()[side].ne(self._pattern(g.backing.device)).nonzero()[0])
+                    off = first - GUARD_BYTES if side == 0 else g.nbytes + first
+                    msgs.append(f"{g.label}: {'front' if side == 0 else 'back'} guard damaged: {count} byte(s), the first at offset {off:+d} from the first byte of the "
+                                f"{g.nbytes}-byte output")
+        raise AssertionError("store outside an output: " + "; ".join(msgs[:8]) + (f"; ... ({len(msgs)} guards in all)" if len(msgs) > 8 else ""))
+
+
+@contextlib.contextmanager
+def checked_outputs():
+    """Inside the block (this thread only) every output the entry points below allocate -- Planes and the copies that cnx_mlp / rb_proj_fc1 update in place included --
+    lies between two GUARD_BYTES guard bands holding guard_pattern(), and every byte of a fresh output is POISON_BYTE (NaN in fp32, fp16 and bf16) before the launch: an
+    element the kernel does not write stays NaN, a store up to GUARD_BYTES outside the output changes a guard.  Yields the CheckedOutputs that keeps every backing buffer
+    alive until the block ends (so no block of the caching allocator comes back holding an earlier launch's result) and compares all guards then, or at `.verify()`:
+    AssertionError on damage.  Past HOLD_LIMIT_BYTES it verifies and releases early.  An exception inside the block is not replaced by a guard report.
+
+    Not covered: a store further than GUARD_BYTES away; out-of-bounds READS; the library-owned buffers of the *_bench entries; with iters > 0 the launches repeat into the
+    same output, whose contents mean nothing then (the guards still do).  thin128(inplace=True) / mit_attn64(inplace=True) run on a guarded copy that is copied back into
+    the caller's tensor: guards only, no poison, and the caller's own allocation is not watched.  conv2d_head's `pn`, a caller's tensor written in part, is left where it is.
+    Not re-entrant: a second checked_outputs() inside the block raises RuntimeError.  Always off again afterwards."""
+    if getattr(_checked, "mgr", None) is not None:
+        raise RuntimeError("checked_outputs() is already active on this thread: it does not nest (call .verify() on the active one for an intermediate check)")
+    mgr = CheckedOutputs()
+    _checked.mgr = mgr
+    try:
+        yield mgr
+    except BaseException:
+        mgr.buffers = []
+        raise
+    finally:
+        _checked.mgr = None
+    mgr.verify()
+
+
+def _out(shape, dtype, device, label, fill=None, poison=True):
+    """Every output allocation of this module.  Outside checked_outputs(): torch.empty (fill None), torch.zeros (fill 0) or torch.full, nothing else.  Inside: a guarded
+    view (CheckedOutputs.allocate): poisoned, or with poison=False holding `fill` (None: left for the caller to copy into)."""
+    import torch
+
+    mgr = getattr(_checked, "mgr", None)
+    if mgr is not None:
+        return mgr.allocate(shape, dtype, device, label, fill, poison)
+    if fill is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if fill == 0:
+        return torch.zeros(shape, dtype=dtype, device=device)
+    return torch.full(shape, fill, dtype=dtype, device=device)
+
+
+def _checking():
+    return getattr(_checked, "mgr", None) is not None
+
+
+def _out_copy(t, label):
+    """a contiguous copy of `t` that a kernel updates in place: t.contiguous().clone(), or inside checked_outputs() the same values between guards"""
+    t = t.contiguous()
+    if not _checking():
+        return t.clone()
+    return _out(t.shape, t.dtype, t.device, label, poison=False).copy_(t)
+
+
 class Planes:
     """An fp32 tensor in one of the engine's split activation formats (include/pf_hip.h): fmt "bf16x3" = three exact bf16
     planes, "f16x2" = the two fp16 planes of the split-f16 scheme.  `plane_elems` carries the format in bit 0."""
@@ -53,7 +199,7 @@ class Planes:
         self.numel = int(np.prod(self.shape))
         stride = (self.numel + 127) // 128 * 128
         self.plane_elems = stride | (1 if fmt == "f16x2" else 0)
-        self.data = torch.zeros((2 if fmt == "f16x2" else 3) * stride, dtype=torch.int16, device=device)
+        self.data = _out((2 if fmt == "f16x2" else 3) * stride, torch.int16, device, "Planes", fill=0)
 
     def data_ptr(self):
         return self.data.data_ptr()
@@ -63,7 +209,7 @@ class Planes:
         import torch
 
         lib = load_library()
-        y = torch.empty(self.shape, dtype=torch.float32, device=self.data.device)
+        y = _out(self.shape, torch.float32, self.data.device, "Planes.merge")
         _check(lib.pf_op_merge_bf16(self.data.device.index, self.data_ptr(), self.plane_elems, self.numel, y.data_ptr(), _stream_ptr()), None, "pf_op_merge_bf16")
         return y
 
@@ -104,7 +250,7 @@ def conv2d(x, weight, bias=None, stride=1, pad=0, act=0, res1=None, res2=None, p
     xp = split_planes(x, planes_fmt) if planes_in else None
     x2p = split_planes(x2, planes_fmt) if (planes_in and x2 is not None) else None
     yp = Planes(shape, x.device, planes_fmt) if planes_out else None
-    y = None if planes_out else torch.empty(shape, dtype=torch.float32, device=x.device)
+    y = None if planes_out else _out(shape, torch.float32, x.device, "conv2d")
     rc = lib.pf_op_conv2d(
         x.device.index, None if planes_in else x.data_ptr(), None if planes_in else _dp(x2), B, H, W, C1, C2, _hp(w), _hp(b),
         Cout, KH, KW, stride, pad, act, _dp(res1), _dp(res2), int(post_relu), int(nchw_out), tile, _dp(y),
@@ -134,7 +280,7 @@ def linear_ln(x, weight, bias, gamma, beta, eps, act=0, res1=None, tile=-1, prec
     rows = x.numel() // K
     w, b, g, be = _np(weight), _np(bias), _np(gamma), _np(beta)
     N = w.shape[0]
-    y = torch.empty((*x.shape[:-1], N), dtype=torch.float32, device=x.device)
+    y = _out((*x.shape[:-1], N), torch.float32, x.device, "linear_ln")
     _check(lib.pf_op_linear_ln(x.device.index, x.data_ptr(), rows, K, _hp(w), _hp(b), _hp(g), _hp(be), float(eps), N, act, _dp(res1), tile, y.data_ptr(), precision,
                                _stream_ptr()), None, "pf_op_linear_ln")
     return y
@@ -152,7 +298,7 @@ def rb_linear(x, weight, bias, tokens, gamma=None, beta=None, eps=1e-6, act=0, r
     w, b = _np(weight), _np(bias)
     g, be = (_np(gamma), _np(beta)) if gamma is not None else (None, None)
     N = w.shape[0]
-    y = torch.empty((*x.shape[:-1], N), dtype=torch.float32, device=x.device)
+    y = _out((*x.shape[:-1], N), torch.float32, x.device, "rb_linear")
     ms = ctypes.c_float()
     _check(lib.pf_op_rb_linear(x.device.index, x.data_ptr(), rows, tokens, K, _hp(w), _hp(b), _hp(g), _hp(be), float(eps), N,
                                act, _dp(res), y.data_ptr(), iters, ctypes.byref(ms), _stream_ptr()), None, "pf_op_rb_linear")
@@ -166,9 +312,9 @@ def rb_proj_fc1(attn, x, proj_w, proj_b, ln2_g, ln2_b, eps, fc1_w, fc1_b, tokens
 
     lib = load_library()
     attn = attn.contiguous()
-    x1 = x.contiguous().clone()
+    x1 = _out_copy(x, "rb_proj_fc1 x1")
     rows, C = attn.shape
-    hidden = torch.empty((rows, 4 * C), dtype=torch.float32, device=attn.device)
+    hidden = _out((rows, 4 * C), torch.float32, attn.device, "rb_proj_fc1 hidden")
     ms = ctypes.c_float()
     a = [_np(t) for t in (proj_w, proj_b, ln2_g, ln2_b, fc1_w, fc1_b)]
     _check(lib.pf_op_rb_proj_fc1(attn.device.index, attn.data_ptr(), x1.data_ptr(), rows // tokens, tokens, C, _hp(a[0]), _hp(a[1]), _hp(a[2]), _hp(a[3]), float(eps), _hp(a[4]), _hp(a[5]),
@@ -184,7 +330,7 @@ def rb_srkv(x, ln1_g, ln1_b, eps1, sr_w, sr_b, srn_g, srn_b, eps2, kv_w, kv_b, i
     lib = load_library()
     x = x.contiguous()
     B, H, W, C = x.shape
-    kv = torch.empty((B, (H // 2) * (W // 2), 2 * C), dtype=torch.float32, device=x.device)
+    kv = _out((B, (H // 2) * (W // 2), 2 * C), torch.float32, x.device, "rb_srkv")
     ms = ctypes.c_float()
     a = [_np(t) for t in (ln1_g, ln1_b, sr_w, sr_b, srn_g, srn_b, kv_w, kv_b)]
     _check(lib.pf_op_rb_srkv(x.device.index, x.data_ptr(), B, H // 2, W // 2, C, _hp(a[0]), _hp(a[1]), float(eps1), _hp(a[2]), _hp(a[3]), _hp(a[4]), _hp(a[5]), float(eps2),
@@ -195,16 +341,19 @@ def rb_srkv(x, ln1_g, ln1_b, eps1, sr_w, sr_b, srn_g, srn_b, eps2, kv_w, kv_b, i
 def mit_attn64(x, kv, ln_gamma, ln_beta, eps, q_w, q_b, proj_w, proj_b, iters=0, inplace=False):
     """y = x + proj(softmax((LN1(x) Wq^T + bq) K^T / 8) V) for (B, N, 64) token rows and (B, M, 128) keys | values in one launch (attn_block.hip).
     iters > 0: returns (y, avg ms per launch)."""
-    import torch
-
     lib = load_library()
     x, kv = x.contiguous(), kv.contiguous()
     B, N, C = x.shape
-    y = x if inplace else torch.empty_like(x)
+    home = x if (inplace and _checking()) else None   # checked: the in-place launch runs on a guarded copy, which is copied back
+    if home is not None:
+        x = _out_copy(x, "mit_attn64 in place")
+    y = x if inplace else _out(x.shape, x.dtype, x.device, "mit_attn64")
     ms = ctypes.c_float()
     g, b, qw, qb, pw, pb = (_np(t) for t in (ln_gamma, ln_beta, q_w, q_b, proj_w, proj_b))
     _check(lib.pf_op_mit_attn64(x.device.index, x.data_ptr(), kv.data_ptr(), y.data_ptr(), B, N, kv.shape[1], _hp(g), _hp(b), eps, _hp(qw), _hp(qb), _hp(pw), _hp(pb),
                                 iters, ctypes.byref(ms), _stream_ptr()), None, "pf_op_mit_attn64")
+    if home is not None:
+        y = home.copy_(y)
     return (y, ms.value) if iters > 0 else y
 
 
@@ -217,7 +366,7 @@ def stem7x7(x4, weight, bias, stride, relu=False, ln_gamma=None, ln_beta=None, e
     x4 = x4.contiguous()
     B, H, W, _ = x4.shape
     Ho, Wo = (H + 6 - 7) // stride + 1, (W + 6 - 7) // stride + 1
-    y = torch.empty((B, Ho, Wo, 64), dtype=torch.float32, device=x4.device)
+    y = _out((B, Ho, Wo, 64), torch.float32, x4.device, "stem7x7")
     ms = ctypes.c_float()
     w, b = _np(weight), _np(bias)
     g, be = (_np(ln_gamma), _np(ln_beta)) if ln_gamma is not None else (None, None)
@@ -229,27 +378,28 @@ def stem7x7(x4, weight, bias, stride, relu=False, ln_gamma=None, ln_beta=None, e
 def thin128(x, weight, bias, res=None, iters=0, inplace=False):
     """x W^T + b (+ res) for a 128 -> 128 layer over (..., 128) rows in the transposed, register-epilogue form (thin_linear.hip).  inplace: y aliases res.
     iters > 0: returns (y, avg ms per launch)."""
-    import torch
-
     lib = load_library()
     x = x.contiguous()
     rows = x.numel() // 128
-    y = res if (inplace and res is not None) else torch.empty_like(x)
+    home = res if (inplace and res is not None and res.is_contiguous() and _checking()) else None   # checked: the in-place launch runs on a guarded copy, which is copied back
+    if home is not None:
+        res = _out_copy(res, "thin128 in place")
+    y = res if (inplace and res is not None) else _out(x.shape, x.dtype, x.device, "thin128")
     ms = ctypes.c_float()
     w, b = _np(weight), _np(bias)
     _check(lib.pf_op_thin128(x.device.index, x.data_ptr(), rows, _hp(w), _hp(b), _dp(res), y.data_ptr(), iters, ctypes.byref(ms), _stream_ptr()), None, "pf_op_thin128")
+    if home is not None:
+        y = home.copy_(y)
     return (y, ms.value) if iters > 0 else y
 
 
 def mit_mlp(x, fc1_w, fc1_b, ln_gamma, ln_beta, eps, dw_w, dw_b, fc2_w, fc2_b, iters=0):
     """One MiT block Mlp in one kernel: x + fc2(GELU(dwconv3x3(fc1(LayerNorm(x))))).  x: (B, Hs, Ws, C) on the GPU, C = 64 or 128.
     iters > 0: returns the average ms per launch instead."""
-    import torch
-
     lib = load_library()
     x = x.contiguous()
     B, Hs, Ws, C = x.shape
-    y = torch.empty_like(x)
+    y = _out(x.shape, x.dtype, x.device, "mit_mlp")
     ms = ctypes.c_float()
     a = [_np(v) for v in (fc1_w, fc1_b, ln_gamma, ln_beta, dw_w, dw_b, fc2_w, fc2_b)]
     _check(lib.pf_op_mit_mlp(x.device.index, x.data_ptr(), y.data_ptr(), B, Hs, Ws, C, _hp(a[0]), _hp(a[1]), _hp(a[2]), _hp(a[3]), float(eps), _hp(a[4]), _hp(a[5]), _hp(a[6]), _hp(a[7]),
@@ -263,7 +413,7 @@ def cnx_mlp(d, y, w1, b1, ln_gamma, ln_beta, eps, w2, b2, layer_scale, iters=0):
     (the row-block form, cnx_rb.hip).  iters > 0: returns (result of the first launch is lost) the average ms per launch."""
     lib = load_library()
     d = d.contiguous()
-    out = y.contiguous().clone()
+    out = _out_copy(y, "cnx_mlp")
     rows, C = d.shape
     ms = ctypes.c_float()
     a = [_np(v) for v in (w1, b1, ln_gamma, ln_beta, w2, b2, layer_scale)]
@@ -273,12 +423,10 @@ def cnx_mlp(d, y, w1, b1, ln_gamma, ln_beta, eps, w2, b2, layer_scale, iters=0):
 
 
 def layernorm(x, gamma, beta, eps, planes_out=False):
-    import torch
-
     lib = load_library()
     x = x.contiguous()
     C = x.shape[-1]
-    y = None if planes_out else torch.empty_like(x)
+    y = None if planes_out else _out(x.shape, x.dtype, x.device, "layernorm")
     yp = Planes(x.shape, x.device) if planes_out else None
     g, b = _np(gamma), _np(beta)
     _check(lib.pf_op_layernorm(x.device.index, x.data_ptr(), _hp(g), _hp(b), _dp(y), x.numel() // C, C, eps, *_pl(yp), _stream_ptr()), None, "pf_op_layernorm")
@@ -287,12 +435,10 @@ def layernorm(x, gamma, beta, eps, planes_out=False):
 
 def dwconv3x3_gelu(x, weight, bias, planes_out=False, variant=None):
     """variant None: the default path; otherwise an explicit kernel (pf_op_dwconv3x3_bench's ids)."""
-    import torch
-
     lib = load_library()
     x = x.contiguous()
     B, H, W, C = x.shape
-    y = None if planes_out else torch.empty_like(x)
+    y = None if planes_out else _out(x.shape, x.dtype, x.device, "dwconv3x3_gelu")
     yp = Planes(x.shape, x.device) if planes_out else None
     w, b = _np(weight), _np(bias)
     if variant is not None:
@@ -305,12 +451,10 @@ def dwconv3x3_gelu(x, weight, bias, planes_out=False, variant=None):
 def dwconv7x7(x, weight, bias, variant=None, nc=0, nb=0, th=0):
     """variant None: the default path; 3: column-blocked streaming kernel (nc columns per thread, nb row buffers, strips of th
     rows; 0 = automatic); 2: one column per lane."""
-    import torch
-
     lib = load_library()
     x = x.contiguous()
     B, H, W, C = x.shape
-    y = torch.empty_like(x)
+    y = _out(x.shape, x.dtype, x.device, "dwconv7x7")
     w, b = _np(weight), _np(bias)
     if variant is None:
         _check(lib.pf_op_dwconv7x7(x.device.index, x.data_ptr(), _hp(w), _hp(b), y.data_ptr(), B, H, W, C, _stream_ptr()), None, "pf_op_dwconv7x7")
@@ -328,13 +472,11 @@ def dwconv7x7_bench(variant, B, H, W, C, nc=0, nb=0, th=0, iters=10, device=0):
 
 def sr_attention(q, kv, heads, planes_out=False):
     """q: (B,N,C), kv: (B,M,2C) -> (B,N,C); head_dim 64."""
-    import torch
-
     lib = load_library()
     q, kv = q.contiguous(), kv.contiguous()
     B, N, C = q.shape
     M = kv.shape[1]
-    out = None if planes_out else torch.empty_like(q)
+    out = None if planes_out else _out(q.shape, q.dtype, q.device, "sr_attention")
     op = Planes(q.shape, q.device) if planes_out else None
     _check(lib.pf_op_sr_attention(q.device.index, q.data_ptr(), kv.data_ptr(), _dp(out), B, N, M, heads, *_pl(op), _stream_ptr()), None, "pf_op_sr_attention")
     return op.merge() if planes_out else out
@@ -342,12 +484,10 @@ def sr_attention(q, kv, heads, planes_out=False):
 
 def sr_attention_variant(q, kv, heads, variant, iters=0):
     """variant 1: split-f16 MFMA kernel (the forward's default), 0: exact fp32 MFMA.  iters > 0: returns (out, avg ms per launch)."""
-    import torch
-
     lib = load_library()
     q, kv = q.contiguous(), kv.contiguous()
     B, N, C = q.shape
-    out = torch.empty_like(q)
+    out = _out(q.shape, q.dtype, q.device, "sr_attention_variant")
     ms = ctypes.c_float()
     _check(lib.pf_op_sr_attention_variant(q.device.index, variant, q.data_ptr(), kv.data_ptr(), out.data_ptr(), B, N, kv.shape[1], heads, iters,
                                           ctypes.byref(ms), _stream_ptr()), None, "pf_op_sr_attention_variant")
@@ -361,7 +501,7 @@ def upsample2x(x, planes_out=False):
     x = x.contiguous()
     B, H, W, C = x.shape
     shape = (B, 2 * H, 2 * W, C)
-    y = None if planes_out else torch.empty(shape, dtype=torch.float32, device=x.device)
+    y = None if planes_out else _out(shape, torch.float32, x.device, "upsample2x")
     yp = Planes(shape, x.device) if planes_out else None
     _check(lib.pf_op_upsample2x(x.device.index, x.data_ptr(), _dp(y), B, H, W, C, *_pl(yp), _stream_ptr()), None, "pf_op_upsample2x")
     return yp.merge() if planes_out else y
@@ -381,7 +521,7 @@ def prep_u8(x_u8, mean3, std3):
     x_u8 = x_u8.contiguous()
     B, H, W, _ = x_u8.shape
     m, s = _np(mean3), _np(std3)
-    y = torch.empty((B, H, W, 4), dtype=torch.float32, device=x_u8.device)
+    y = _out((B, H, W, 4), torch.float32, x_u8.device, "prep_u8")
     _check(lib.pf_op_prep_u8(x_u8.device.index, x_u8.data_ptr(), B, H, W, _hp(m), _hp(s), y.data_ptr(), _stream_ptr()), None, "pf_op_prep_u8")
     return y
 
@@ -394,7 +534,7 @@ def prep_f32_nchw(x, mean3, std3):
     x = x.contiguous()
     B, _, H, W = x.shape
     m, s = _np(mean3), _np(std3)
-    y = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
+    y = _out((B, H, W, 4), torch.float32, x.device, "prep_f32_nchw")
     _check(lib.pf_op_prep_f32_nchw(x.device.index, x.data_ptr(), B, H, W, _hp(m), _hp(s), y.data_ptr(), _stream_ptr()), None, "pf_op_prep_f32_nchw")
     return y
 
@@ -407,9 +547,9 @@ def pred_regression(tg, tl, wg, bg, wl, bl, with_pn=True, pn_fill=None):
     tg, tl = tg.contiguous(), tl.contiguous()
     B, HW, _ = tg.shape
     a = [_np(t) for t in (wg, bg, wl, bl)]
-    pg = torch.empty((B, 2, HW), dtype=torch.float32, device=tg.device)
-    pl = torch.empty((B, HW), dtype=torch.float32, device=tg.device)
-    pn = torch.full((B * HW, 4), float("nan") if pn_fill is None else pn_fill, dtype=torch.float32, device=tg.device) if with_pn else None
+    pg = _out((B, 2, HW), torch.float32, tg.device, "pred_regression pg")
+    pl = _out((B, HW), torch.float32, tg.device, "pred_regression pl")
+    pn = _out((B * HW, 4), torch.float32, tg.device, "pred_regression pn", fill=float("nan") if pn_fill is None else pn_fill, poison=False) if with_pn else None
     _check(lib.pf_op_pred_regression(tg.device.index, tg.data_ptr(), tl.data_ptr(), B, HW, _hp(a[0]), _hp(a[1]), _hp(a[2]), _hp(a[3]), pg.data_ptr(), pl.data_ptr(), _dp(pn),
                                      _stream_ptr()), None, "pf_op_pred_regression")
     return pg, pl, pn
@@ -423,8 +563,8 @@ def decode_cls(logit_g, logit_l):
     logit_g, logit_l = logit_g.contiguous(), logit_l.contiguous()
     B, ng, HW = logit_g.shape
     nl = logit_l.shape[1]
-    dg = torch.empty((B, 2, HW), dtype=torch.float32, device=logit_g.device)
-    dl = torch.empty((B, HW), dtype=torch.float32, device=logit_g.device)
+    dg = _out((B, 2, HW), torch.float32, logit_g.device, "decode_cls dg")
+    dl = _out((B, HW), torch.float32, logit_g.device, "decode_cls dl")
     _check(lib.pf_op_decode_cls(logit_g.device.index, logit_g.data_ptr(), ng, logit_l.data_ptr(), nl, B, HW, dg.data_ptr(), dl.data_ptr(), _stream_ptr()), None, "pf_op_decode_cls")
     return dg, dl
 
@@ -436,7 +576,7 @@ def nearest_nhwc4(x, Ho, Wo):
     lib = load_library()
     x = x.contiguous()
     B, H, W, _ = x.shape
-    y = torch.empty((B, Ho, Wo, 4), dtype=torch.float32, device=x.device)
+    y = _out((B, Ho, Wo, 4), torch.float32, x.device, "nearest_nhwc4")
     _check(lib.pf_op_nearest_nhwc4(x.device.index, x.data_ptr(), B, H, W, Ho, Wo, y.data_ptr(), _stream_ptr()), None, "pf_op_nearest_nhwc4")
     return y
 
@@ -450,7 +590,7 @@ def gap_ln_head(x, gamma, beta, eps, head_w, head_b):
     B, HW, C = x.shape
     g, b, w, hb = (_np(t) for t in (gamma, beta, head_w, head_b))
     nout = w.shape[0]
-    y = torch.empty((B, nout), dtype=torch.float32, device=x.device)
+    y = _out((B, nout), torch.float32, x.device, "gap_ln_head")
     _check(lib.pf_op_gap_ln_head(x.device.index, x.data_ptr(), B, HW, C, _hp(g), _hp(b), float(eps), _hp(w), _hp(hb), nout, y.data_ptr(), _stream_ptr()), None, "pf_op_gap_ln_head")
     return y
 
@@ -462,7 +602,7 @@ def paramnet_scalars(raw, mode):
     lib = load_library()
     raw = raw.contiguous()
     B, nraw = raw.shape
-    out = torch.full((B, 8), float("nan"), dtype=torch.float32, device=raw.device)
+    out = _out((B, 8), torch.float32, raw.device, "paramnet_scalars", fill=float("nan"))
     _check(lib.pf_op_paramnet_scalars(raw.device.index, raw.data_ptr(), B, nraw, int(mode), out.data_ptr(), _stream_ptr()), None, "pf_op_paramnet_scalars")
     return out
 
@@ -484,7 +624,7 @@ def conv2d_head(x, weight, bias, act, head_kind, head_w, head_b, tile=-1, pn=Non
     w, b, hw, hb = _np(weight), _np(bias), _np(head_w), _np(head_b)
     if w.shape != (32, Cin, 3, 3):
         raise PfError(f"weight shape {w.shape} != (32, {Cin}, 3, 3)")
-    out = torch.empty((B, 2, H * W) if head_kind == 1 else (B, H * W), dtype=torch.float32, device=x.device)
+    out = _out((B, 2, H * W) if head_kind == 1 else (B, H * W), torch.float32, x.device, "conv2d_head")
     _check(lib.pf_op_conv2d_head(x.device.index, x.data_ptr(), B, H, W, Cin, _hp(w), _hp(b), int(act), int(head_kind), _hp(hw), _hp(hb), int(tile), out.data_ptr(), _dp(pn),
                                  _stream_ptr()), None, "pf_op_conv2d_head")
     return out

@@ -25,6 +25,14 @@ def ops():
     return _ops
 
 
+@pytest.fixture(autouse=True)
+def _checked_outputs(ops):
+    """every test of this module runs inside ops.checked_outputs(): each output an entry point allocates is NaN before its launch, lies
+    between guard bands that are compared when the test ends, and no block comes back from the allocator holding an earlier launch's result"""
+    with ops.checked_outputs():
+        yield
+
+
 def _rand(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(shape, generator=g, dtype=torch.float32) * scale
