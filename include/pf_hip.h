@@ -1082,6 +1082,26 @@ int pf_op_conv2d_head_tile_usable(int B, int H, int W, int Cin, int act, int hea
 int pf_op_conv2d_head(int device, const float* d_x, int B, int H, int W, int Cin, const float* h_weight /*[32][Cin][3][3]*/, const float* h_bias /*[32] or NULL*/, int act,
                       int head_kind, const float* h_head_w /*[nout][32]*/, const float* h_head_b /*[nout]*/, int tile_id, float* d_head_out, float* d_pn /*or NULL*/,
                       void* stream);
+/* The conv forms that only the forward's grouped launches set (tests/test_gpu_conv_forms.py): `groups` (1 or 2) problems of one shape in one grid, as the two decoder
+ * heads run; ups = 1: the first input is stored at HALF resolution, (B, H/2, W/2, C1), and the conv runs on its bilinear x2 up-sampling (align_corners = False),
+ * interpolated while the halo is staged -- H, W are the full-resolution size, d_x2 (C2 channels, concatenated behind) is at full resolution; bias_rows[g] = 9: h_bias[g]
+ * is the [9][Cout] border-case table of a folded Linear -> zero-padded 3x3 pair, row 3 cy + cx with cy = 0 on the first output row, 2 on the last, 1 between, cx likewise
+ * by column; head_kind[g] = 1 / 2: the prediction head of pf_op_conv2d_head in group g's epilogue (then d_y[g] is not used; d_pn[g] optional, both groups may give the same
+ * buffer: kind 1 writes floats 0-1 of a row, kind 2 floats 2-3).  Every per-group argument is a HOST array of `groups` pointers (d_x2, h_bias, d_res1, d_res2, d_y, the
+ * head arrays and d_pn may be NULL as a whole when no group uses them); shape, stride, pad, act, post_relu, ups, tile and precision (0 split-f16 or 3 exact bf16 split)
+ * are shared.  Weights are packed as pf_op_conv2d packs them.  splitk_mode -1: split-K by the engine's rule (conv_splitk_factor), 0: never, N > 1: that factor where the
+ * rule allows split-K at all; it runs on the linear split tiles only, and *splitk_used (optional) receives the factor the launch really used (1 = none).
+ * Preconditions, each PF_ERR_ARG before any device work (no device is asked for, nothing uploaded, nothing launched) and never a fallback: groups 1 or 2; C1 and C2 multiples of 32; precision 0 or 3; ups needs even H and W and
+ * precision 0; a bias table needs Ho >= 2 and Wo >= 2 (a pixel that is both the first and the last row or column is none of the nine cases); a fused head needs
+ * Cout == 32, and either every group has one or none; a tile id that cannot run the form (pf_op_conv2d_g_tile_usable says which can, host logic only: 1 / 0; its
+ * has_table and head_kind hold for every group), and tile_id -1 when the cost model's tile cannot run it. */
+int pf_op_conv2d_g_tile_usable(int B, int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad, int act, int groups, int ups, int has_table, int head_kind,
+                               int precision, int tile_id);
+int pf_op_conv2d_g(int device, int groups, const float* const* d_x, const float* const* d_x2, int B, int H, int W, int C1, int C2,
+                   const float* const* h_weight /*[Cout][C1+C2][KH][KW] each*/, const float* const* h_bias /*[Cout] or [9][Cout] each, or NULL*/, const int* bias_rows /*1 or 9*/,
+                   int Cout, int KH, int KW, int stride, int pad, int act, const float* const* d_res1, const float* const* d_res2, int post_relu, int ups,
+                   float* const* d_y, const int* head_kind, const float* const* h_head_w, const float* const* h_head_b, float* const* d_head_out, float* const* d_pn,
+                   int tile_id, int precision, int splitk_mode, int* splitk_used, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,11 @@ using namespace pf_host;
 static thread_local unsigned* t_op_sat = nullptr;
 static thread_local float t_op_sat_limit = 65504.f;
 
+// the form whose weights the conv entries also pack for the Winograd tiles ("wino256x64d" / "wino256x64c"); the launch's own rule is conv_wino_ok
+static bool conv_wino_form(int KH, int KW, int stride, int pad, int C2, int Cin, int Cout, int KWC, int KWCp) {
+  return KH == 3 && KW == 3 && stride == 1 && pad == 1 && C2 == 0 && Cin % 16 == 0 && Cout % 64 == 0 && KWCp == KWC;
+}
+
 extern "C" {
 
 int pf_op_set_saturation_watch(void* d_counter_u32, float limit) {
@@ -44,7 +49,7 @@ int pf_op_conv2d(int device, const float* x, const float* x2, int B, int H, int 
     const F16Planes f = split_f16x2(packed, Cout);
     p.g[0].w_h16 = tmp.up_u16(f.planes); p.g[0].w_h16_inv_scale = tmp.up(f.inv_scale);
   }
-  if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && C2 == 0 && Cin % 16 == 0 && Cout % 64 == 0 && p.KWCp == p.KWC) {  // Winograd form (tiles "wino256x64d" / "wino256x64c")
+  if (conv_wino_form(KH, KW, stride, pad, C2, Cin, Cout, p.KWC, p.KWCp)) {
     std::vector<unsigned short> planes;
     std::vector<float> inv;
     wino_pack_weights(packed.data(), Cout, Cin, p.KWCp, &planes, &inv);
@@ -876,6 +881,171 @@ int pf_op_conv2d_head(int device, const float* x, int B, int H, int W, int Cin, 
   }
   if (tile_id < 0 && !conv_tile_usable(p, conv_default_tile(p))) { g_create_error = "pf_op_conv2d_head: no tile runs this shape"; tmp.sync_free(s); return PF_ERR_ARG; }
   launch_conv_tile(p, tile_id, s);
+  const int out = hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
+  tmp.sync_free(s);
+  return out;
+}
+
+// ---- the conv forms only the forward's conv_g sets (engine_forward.hip): two problems in one grid, the first input at half resolution, the nine-case bias table
+struct ConvGShape { int B, H, W, C1, C2, Cout, KH, KW, stride, pad, act, groups, ups, precision; };
+static const char* conv2d_g_shape_error(const ConvGShape& c, const int* has_table, const int* head_kind) {
+  if (c.groups != 1 && c.groups != 2) return "groups must be 1 or 2";
+  if (c.precision != PF_PRECISION_FP32 && c.precision != PF_PRECISION_FP32_BF16X6) return "precision must be 0 (split-f16) or 3 (exact bf16 split)";
+  if (c.B < 1 || c.H < 1 || c.W < 1 || c.C1 < 1 || c.C2 < 0 || c.Cout < 1 || c.KH < 1 || c.KW < 1 || c.stride < 1 || c.pad < 0) return "B, H, W, C1, Cout, KH, KW, stride >= 1 and C2, pad >= 0 required";
+  if (c.H + 2 * c.pad < c.KH || c.W + 2 * c.pad < c.KW) return "the kernel does not fit the padded map";
+  if (c.C1 % 32 != 0 || c.C2 % 32 != 0) return "C1 and C2 must be multiples of 32";
+  if ((long)c.B * c.H * c.W * std::max(std::max(c.C1, c.C2), c.Cout) * 4 >= 0x7fffffffL || (long)c.Cout * c.KH * roundup(c.KW * (c.C1 + c.C2), 32) * 4 >= 0x7fffffffL) return "tensors of 2 GiB and more are not addressable";
+  if (c.act != ACT_NONE && c.act != ACT_RELU && c.act != ACT_GELU) return "act must be 0 (none), 1 (relu) or 2 (gelu)";
+  if (c.ups != 0 && c.ups != 1) return "ups must be 0 or 1";
+  if (c.ups && ((c.H & 1) || (c.W & 1))) return "ups: H and W (the full-resolution size) must be even";
+  if (c.ups && c.precision != PF_PRECISION_FP32) return "ups: the halo tiles interpolate in the split-f16 scheme only (precision 0)";
+  const int Ho = (c.H + 2 * c.pad - c.KH) / c.stride + 1, Wo = (c.W + 2 * c.pad - c.KW) / c.stride + 1;
+  for (int g = 0; g < c.groups; ++g) {
+    if (has_table[g] && (Ho < 2 || Wo < 2)) return "a bias table needs Ho >= 2 and Wo >= 2: a pixel that is both the first and the last row (column) is none of the nine border cases";
+    if (head_kind[g] < 0 || head_kind[g] > 2) return "head_kind must be 0 (none), 1 (gravity) or 2 (latitude)";
+    if ((head_kind[g] != 0) != (head_kind[0] != 0)) return "every group has a fused head or none has";
+    if (head_kind[g] && c.Cout != 32) return "a fused head needs Cout == 32";
+  }
+  return nullptr;
+}
+// the shape fields of the launch; the operands of the usability rules (which exist, never what they hold) from `dummy` when the caller has no real ones yet
+static void conv2d_g_params(ConvParams* p, const ConvGShape& c, const int* has_table, const int* head_kind, bool dummies) {
+  static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
+  static const unsigned short dummy16[2] = {0, 0};
+  static float dummy_out[4];
+  p->groups = c.groups;
+  p->KWC = c.KW * (c.C1 + c.C2); p->KWCp = roundup(p->KWC, 32);
+  p->B = c.B; p->H = c.H; p->W = c.W; p->C1 = c.C1; p->C2 = c.C2; p->KH = c.KH; p->KW = c.KW; p->stride = c.stride; p->pad = c.pad;
+  p->Cout = c.Cout; p->act = c.act; p->post_relu = 0; p->nchw_out = 0; p->ups = c.ups;
+  p->nterms = c.precision == PF_PRECISION_FP32_BF16X6 ? 6 : NT_F16X3;
+  p->wino_half = conv_wino_half_env();
+  for (int g = 0; g < c.groups; ++g) p->g[g].head_kind = head_kind[g];
+  p->finish();
+  if (!dummies) return;
+  const bool wino_form = conv_wino_form(c.KH, c.KW, c.stride, c.pad, c.C2, c.C1 + c.C2, c.Cout, p->KWC, p->KWCp);
+  for (int g = 0; g < c.groups; ++g) {
+    ConvPtrs& q = p->g[g];
+    q.x = dummy; q.x2 = c.C2 > 0 ? dummy : nullptr; q.w = dummy; q.w_sb = dummy16; q.w_h16 = dummy16; q.w_h16_inv_scale = dummy;
+    if (wino_form) { q.w_wino = dummy16; q.w_wino_inv = dummy; }
+    if (has_table[g]) q.bias_tab = dummy; else q.bias = dummy;
+    if (head_kind[g]) { q.head_w = dummy; q.head_b = dummy; q.head_out = dummy_out; } else q.y = dummy_out;
+  }
+}
+
+// the tile and the split-K factor (linear split tiles only; the engine's rule or the caller's mode) of a launch, from which operands exist -- dummy or real;
+// "" or why nothing runs the form.  launch_conv_tile would replace a tile that cannot run it, and launch_sbh_cfg returns without a launch for an up-sampling form
+// on a tile that is not a 4-wave plain-tap tile: neither may be reached
+static std::string conv2d_g_plan(ConvParams p, int tile_id, int splitk_mode, int* tile, int* S) {
+  *tile = tile_id >= 0 ? tile_id : conv_default_tile(p);
+  *S = 1;
+  if (!conv_tile_usable(p, *tile)) return tile_id >= 0 ? fmt("tile %d (%s) cannot run this form", tile_id, conv_tile_name(tile_id)) : std::string("no tile runs this form");
+  const char* nm = conv_tile_name(*tile);
+  if (!conv_tile_is_sb(*tile) || strncmp(nm, "sbh", 3) == 0 || strncmp(nm, "wino", 4) == 0) return "";
+  *S = splitk_mode < 0 ? conv_splitk_factor(p) : conv_splitk_factor(p, splitk_mode);
+  if (*S > 1) {
+    p.splitk = *S;
+    for (int g = 0; g < p.groups; ++g) p.g[g].partial = p.g[g].y;  // exists; nothing here reads it
+    if (!conv_tile_usable(p, *tile)) return "the tile cannot run the split-K form";
+  }
+  return "";
+}
+
+int pf_op_conv2d_g_tile_usable(int B, int H, int W, int C1, int C2, int Cout, int KH, int KW, int stride, int pad, int act, int groups, int ups, int has_table, int head_kind,
+                               int precision, int tile_id) {
+  const ConvGShape c{B, H, W, C1, C2, Cout, KH, KW, stride, pad, act, groups, ups, precision};
+  const int tab[2] = {has_table ? 1 : 0, has_table ? 1 : 0}, hk[2] = {head_kind, head_kind};
+  if (conv2d_g_shape_error(c, tab, hk)) return 0;
+  ConvParams p;
+  conv2d_g_params(&p, c, tab, hk, true);
+  return conv_tile_usable(p, tile_id) ? 1 : 0;
+}
+
+int pf_op_conv2d_g(int device, int groups, const float* const* d_x, const float* const* d_x2, int B, int H, int W, int C1, int C2, const float* const* h_weight,
+                   const float* const* h_bias, const int* bias_rows, int Cout, int KH, int KW, int stride, int pad, int act, const float* const* d_res1,
+                   const float* const* d_res2, int post_relu, int ups, float* const* d_y, const int* head_kind, const float* const* h_head_w, const float* const* h_head_b,
+                   float* const* d_head_out, float* const* d_pn, int tile_id, int precision, int splitk_mode, int* splitk_used, void* stream) {
+  if (splitk_used) *splitk_used = 1;
+  if (!d_x || !h_weight || !bias_rows || !head_kind) return op_arg_error("pf_op_conv2d_g: d_x, h_weight, bias_rows, head_kind (arrays of `groups` entries) required");
+  const ConvGShape c{B, H, W, C1, C2, Cout, KH, KW, stride, pad, act, groups, ups, precision};
+  int tab[2] = {0, 0}, hk[2] = {0, 0};
+  for (int g = 0; g < std::min(std::max(groups, 0), 2); ++g) {
+    if (bias_rows[g] != 1 && bias_rows[g] != 9) return op_arg_error("pf_op_conv2d_g: bias_rows must be 1 ([Cout]) or 9 ([9][Cout])");
+    tab[g] = bias_rows[g] == 9; hk[g] = head_kind[g];
+  }
+  if (const char* e = conv2d_g_shape_error(c, tab, hk)) { g_create_error = std::string("pf_op_conv2d_g: ") + e; return PF_ERR_ARG; }
+  if (tile_id < -1 || tile_id >= conv_num_tiles()) return op_arg_error("pf_op_conv2d_g: tile_id must be -1 (automatic) or a tile id");
+  if (splitk_mode < -1 || splitk_mode == 1) return op_arg_error("pf_op_conv2d_g: splitk_mode must be -1 (the engine's rule), 0 (never) or a factor above 1");
+  for (int g = 0; g < groups; ++g) {
+    if (!d_x[g] || !aligned16(d_x[g]) || !h_weight[g] || (C2 > 0 && (!d_x2 || !d_x2[g] || !aligned16(d_x2[g]))) || (tab[g] && (!h_bias || !h_bias[g])))
+      return op_arg_error("pf_op_conv2d_g: every group needs d_x (16-byte aligned), h_weight, d_x2 when C2 > 0, and its table when bias_rows is 9");
+    if (hk[g] ? (!h_head_w || !h_head_w[g] || !h_head_b || !h_head_b[g] || !d_head_out || !d_head_out[g] || (d_pn && d_pn[g] && !aligned16(d_pn[g]))) : (!d_y || !d_y[g] || !aligned16(d_y[g])))
+      return op_arg_error("pf_op_conv2d_g: every group needs d_y (16-byte aligned), or with a fused head head_w, head_b, head_out (pn optional, 16-byte aligned)");
+    if ((d_res1 && d_res1[g] && !aligned16(d_res1[g])) || (d_res2 && d_res2[g] && !aligned16(d_res2[g]))) return op_arg_error("pf_op_conv2d_g: residuals must be 16-byte aligned");
+  }
+  int tile = -1, S = 1;
+  {  // the tile and the split-K factor on the dummy operand set of the usability query, with the residuals as given: decided before any device work
+    ConvParams probe;
+    conv2d_g_params(&probe, c, tab, hk, true);
+    probe.post_relu = post_relu;
+    for (int g = 0; g < groups; ++g) { probe.g[g].res1 = d_res1 ? d_res1[g] : nullptr; probe.g[g].res2 = d_res2 ? d_res2[g] : nullptr; }
+    const std::string e = conv2d_g_plan(probe, tile_id, splitk_mode, &tile, &S);
+    if (!e.empty()) { g_create_error = "pf_op_conv2d_g: " + e; return PF_ERR_ARG; }
+  }
+  const int rc = op_begin(device);
+  if (rc != PF_OK) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TmpDev tmp;
+  ConvParams p;
+  conv2d_g_params(&p, c, tab, hk, false);
+  p.post_relu = post_relu;
+  p.sat = t_op_sat; p.sat_limit = t_op_sat_limit;
+  const int Cin = C1 + C2;
+  bool up_ok = true;
+  for (int g = 0; g < groups; ++g) {  // weights packed as pf_op_conv2d packs them
+    ConvPtrs& q = p.g[g];
+    int kwc = 0, kwcp = 0;
+    const std::vector<float> packed = pack_conv(h_weight[g], Cout, Cin, KH, KW, Cin, nullptr, &kwc, &kwcp);
+    q.w = tmp.up(packed);
+    q.w_sb = tmp.up_u16(split_bf16x3(packed));
+    const F16Planes f = split_f16x2(packed, Cout);
+    q.w_h16 = tmp.up_u16(f.planes); q.w_h16_inv_scale = tmp.up(f.inv_scale);
+    up_ok = up_ok && q.w && q.w_sb && q.w_h16 && q.w_h16_inv_scale;
+    if (conv_wino_form(KH, KW, stride, pad, C2, Cin, Cout, p.KWC, p.KWCp)) {
+      std::vector<unsigned short> planes;
+      std::vector<float> inv;
+      wino_pack_weights(packed.data(), Cout, Cin, p.KWCp, &planes, &inv);
+      q.w_wino = tmp.up_u16(planes); q.w_wino_inv = tmp.up(inv);
+      up_ok = up_ok && q.w_wino && q.w_wino_inv;
+    }
+    const float* hb = h_bias ? h_bias[g] : nullptr;
+    if (tab[g]) q.bias_tab = tmp.up(hb, (size_t)9 * Cout); else q.bias = tmp.up(hb, Cout);
+    up_ok = up_ok && (!hb || q.bias || q.bias_tab);
+    q.x = d_x[g]; q.x2 = C2 > 0 ? d_x2[g] : nullptr; q.res1 = d_res1 ? d_res1[g] : nullptr; q.res2 = d_res2 ? d_res2[g] : nullptr;
+    if (hk[g]) {
+      const int nout = hk[g] == 1 ? 2 : 1;
+      q.head_w = tmp.up(h_head_w[g], (size_t)nout * 32); q.head_b = tmp.up(h_head_b[g], nout);
+      q.head_out = d_head_out[g]; q.head_pn = d_pn ? d_pn[g] : nullptr;
+      up_ok = up_ok && q.head_w && q.head_b;
+    } else {
+      q.y = d_y[g];
+    }
+  }
+  if (!up_ok) { g_create_error = "pf_op_conv2d_g: hipMalloc failed"; tmp.sync_free(s); return PF_ERR_DEVICE; }
+  if (S > 1) {  // the scratch laid out as conv_g lays it out: group g at part + g S M Cout
+    void* d = nullptr;
+    if (hipMalloc(&d, (size_t)S * groups * p.M * p.Cout * 4) != hipSuccess) { g_create_error = "pf_op_conv2d_g: hipMalloc failed"; tmp.sync_free(s); return PF_ERR_DEVICE; }
+    tmp.p.push_back(d);
+    for (int g = 0; g < groups; ++g) p.g[g].partial = static_cast<float*>(d) + (size_t)g * S * p.M * p.Cout;
+    p.splitk = S;
+  }
+  if (!conv_tile_usable(p, tile)) {  // the real operand set must meet the rules the plan met
+    g_create_error = fmt("pf_op_conv2d_g: tile %d (%s) refuses the uploaded operands", tile, conv_tile_name(tile));
+    tmp.sync_free(s);
+    return PF_ERR_ARG;
+  }
+  const long splitk_before = g_launch_counts.splitk;
+  launch_conv_tile(p, tile, s);
+  if (splitk_used && g_launch_counts.splitk != splitk_before) *splitk_used = p.splitk;  // what launch_conv_sb really did
   const int out = hipGetLastError() == hipSuccess ? PF_OK : PF_ERR_DEVICE;
   tmp.sync_free(s);
   return out;

@@ -132,12 +132,13 @@ int conv_splitk_shape(long M, int Cout, int KH, int KWCp, int groups, int mode) 
   while (S > 1 && nK / S < 8) --S;
   return S;
 }
-int conv_splitk_factor(const ConvParams& p) {
+int conv_splitk_factor(const ConvParams& p, int mode) {
   if (p.nchw_out || p.ups || p.ln || (p.Cin % BK) != 0 || !conv_sb_eligible(p)) return 1;
   for (int g = 0; g < p.groups; ++g)
     if (p.g[g].head_kind || p.g[g].bias_tab || p.g[g].res2 || p.g[g].y_sb || !p.g[g].y) return 1;
-  return conv_splitk_shape(p.M, p.Cout, p.KH, p.KWCp, p.groups, conv_splitk_env());
+  return conv_splitk_shape(p.M, p.Cout, p.KH, p.KWCp, p.groups, mode);
 }
+int conv_splitk_factor(const ConvParams& p) { return conv_splitk_factor(p, conv_splitk_env()); }
 
 // y = post(act(oscale * sum_s partial[s] + bias) + res1), 4 outputs per thread.  This kernel writes the layer's finished output, so the saturation watch of a split-K
 // layer (ConvParams::sat) lives here: the partial passes are not watched

@@ -157,6 +157,7 @@ void launch_conv_sb(const ConvParams& p, int sb_tile, hipStream_t s);
 // split-K factor for a launch (1 = none): deep-K shapes whose 64x64 tiling gives too few blocks for 256 CUs (the MiT spatial-
 // reduction convs: 3 200 rows, K up to 4 096); the caller allocates g[].partial = splitk * M * ldy floats and sets ConvParams::splitk
 int conv_splitk_factor(const ConvParams& p);
+int conv_splitk_factor(const ConvParams& p, int mode);  // the same with the caller's mode in place of PF_SPLITK (mode as in conv_splitk_shape)
 int conv_splitk_shape(long M, int Cout, int KH, int KWCp, int groups, int mode);  // its shape-only part; mode = PF_SPLITK (conv_splitk_env): -1 default, 0 never, N > 1 forces the factor
 int conv_wino_half_env();  // PF_WINO_HALF (default 1) as the environment has it NOW
 int conv_splitk_env();  // PF_SPLITK as the environment has it NOW (pf_create reads it per engine, the op entry points per call: tests switch it inside one process)

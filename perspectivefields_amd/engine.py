@@ -144,6 +144,10 @@ _SIGNATURES = {
     "pf_op_paramnet_scalars": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
     "pf_op_conv2d_head_tile_usable": (_c.c_int, [_c.c_int] * 7),
     "pf_op_conv2d_head": (_c.c_int, [_c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _P, _P]),
+    "pf_op_conv2d_g_tile_usable": (_c.c_int, [_c.c_int] * 17),
+    "pf_op_conv2d_g": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P,
+                                  _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int,
+                                  _P, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _P]),
 }
 
 _lib = None

@@ -144,7 +144,7 @@ def checked_outputs():
 
     Not covered: a store further than GUARD_BYTES away; out-of-bounds READS; the library-owned buffers of the *_bench entries; with iters > 0 the launches repeat into the
     same output, whose contents mean nothing then (the guards still do).  thin128(inplace=True) / mit_attn64(inplace=True) run on a guarded copy that is copied back into
-    the caller's tensor: guards only, no poison, and the caller's own allocation is not watched.  conv2d_head's `pn`, a caller's tensor written in part, is left where it is.
+    the caller's tensor: guards only, no poison, and the caller's own allocation is not watched.  The `pn` of conv2d_head and conv2d_g, a caller's tensor written in part, is left where it is.
     Not re-entrant: a second checked_outputs() inside the block raises RuntimeError.  Always off again afterwards."""
     if getattr(_checked, "mgr", None) is not None:
         raise RuntimeError("checked_outputs() is already active on this thread: it does not nest (call .verify() on the active one for an intermediate check)")
@@ -628,6 +628,59 @@ def conv2d_head(x, weight, bias, act, head_kind, head_w, head_b, tile=-1, pn=Non
     _check(lib.pf_op_conv2d_head(x.device.index, x.data_ptr(), B, H, W, Cin, _hp(w), _hp(b), int(act), int(head_kind), _hp(hw), _hp(hb), int(tile), out.data_ptr(), _dp(pn),
                                  _stream_ptr()), None, "pf_op_conv2d_head")
     return out
+
+
+def conv2d_g_tiles(B, H, W, C1, Cout, K, stride=1, pad=0, act=0, groups=1, ups=False, C2=0, has_table=False, head_kind=0, precision=0):
+    """ids of the conv tiles that can run a form of pf_op_conv2d_g (host logic only: no GPU needed).  H, W: the full-resolution size."""
+    lib = load_library()
+    return [t for t in range(lib.pf_op_num_conv_tiles())
+            if lib.pf_op_conv2d_g_tile_usable(B, H, W, C1, C2, Cout, K, K, stride, pad, act, groups, int(ups), int(has_table), head_kind, precision, t)]
+
+
+def conv2d_g(problems, stride=1, pad=0, act=0, post_relu=False, ups=False, tile=-1, precision=0, splitk=-1, size=None):
+    """One grouped launch (pf_op_conv2d_g) of len(problems) = 1 or 2 convs of one shape.  A problem is a dict: x (B,H,W,C1), or with ups (B,H/2,W/2,C1) at half
+    resolution; weight (Cout,C1+C2,KH,KW); optional x2 (B,H,W,C2), bias ((Cout,), or (9,Cout): the border-case table), res1, res2, and for a fused head head_kind (1 / 2),
+    head_w, head_b and pn ((B*H*W,4), partly written in place; the groups may share one).  splitk: -1 the engine's rule, 0 never, N > 1 that factor.
+    size: the full-resolution (H, W) when it is not the one x implies (with ups an odd size, which the entry refuses).
+    Returns (outputs, factor): per problem y (B,Ho,Wo,Cout) or the head output ((B,2,Ho*Wo) / (B,Ho*Wo)), and the split-K factor the launch used (1 = none).
+    A tile that cannot run the form raises."""
+    import torch
+
+    lib = load_library()
+    n = len(problems)
+    if n not in (1, 2):
+        raise PfError("conv2d_g: one or two problems")
+    xs = [pr["x"].contiguous() for pr in problems]
+    B, Hs, Ws, C1 = xs[0].shape
+    H, W = size if size is not None else ((2 * Hs, 2 * Ws) if ups else (Hs, Ws))
+    ws = [_np(pr["weight"]) for pr in problems]
+    Cout, Cin, KH, KW = ws[0].shape
+    C2 = Cin - C1
+    x2s = [pr["x2"].contiguous() if pr.get("x2") is not None else None for pr in problems]
+    bs = [_np(pr.get("bias")) for pr in problems]
+    rows = [9 if (b is not None and b.ndim == 2) else 1 for b in bs]
+    kinds = [int(pr.get("head_kind", 0)) for pr in problems]
+    hws, hbs = [_np(pr.get("head_w")) for pr in problems], [_np(pr.get("head_b")) for pr in problems]
+    for x, w, x2, b, r in zip(xs, ws, x2s, bs, rows):
+        if x.shape != xs[0].shape or w.shape != ws[0].shape or (x2 is None) != (C2 == 0) or (x2 is not None and tuple(x2.shape) != (B, H, W, C2)):
+            raise PfError("conv2d_g: the problems of one launch share one shape; x2 (B,H,W,C2) exactly when the weight has more input channels than x")
+        if b is not None and b.shape != ((9, Cout) if r == 9 else (Cout,)):
+            raise PfError(f"conv2d_g: bias shape {b.shape} is neither ({Cout},) nor (9, {Cout})")
+    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    outs = [_out(((B, 2, Ho * Wo) if k == 1 else (B, Ho * Wo)) if k else (B, Ho, Wo, Cout), torch.float32, xs[0].device, "conv2d_g") for k in kinds]
+
+    def arr(vals, host=False):
+        return (ctypes.c_void_p * n)(*[(v.ctypes.data if v is not None else None) if host else _dp(v) for v in vals])
+
+    ints = lambda vals: (ctypes.c_int * n)(*vals)
+    used = ctypes.c_int(1)
+    rc = lib.pf_op_conv2d_g(
+        xs[0].device.index, n, arr(xs), arr(x2s), B, H, W, C1, C2, arr(ws, True), arr(bs, True), ints(rows), Cout, KH, KW, stride, pad, int(act),
+        arr([pr.get("res1") for pr in problems]), arr([pr.get("res2") for pr in problems]), int(post_relu), int(ups),
+        arr([None if k else o for k, o in zip(kinds, outs)]), ints(kinds), arr(hws, True), arr(hbs, True), arr([o if k else None for k, o in zip(kinds, outs)]),
+        arr([pr.get("pn") for pr in problems]), int(tile), int(precision), int(splitk), ctypes.byref(used), _stream_ptr())
+    _check(rc, None, "pf_op_conv2d_g")
+    return outs, used.value
 
 
 def conv2d_bench(B, H, W, Cin, Cout, K, stride=1, pad=0, tile=-1, iters=10, device=0, fmt=0, precision=0):

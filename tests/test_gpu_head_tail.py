@@ -15,10 +15,9 @@ import torch
 import torch.nn.functional as F
 
 from oracle import pf_oracle
+from tests.kernel_bounds import U, _head_bounds, _normalize_bounds, _ratio
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -24  # fp32 unit roundoff
 
 
 @pytest.fixture(scope="module")
@@ -39,13 +38,6 @@ def _checked_outputs(ops):
 def _rand(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(shape, generator=g, dtype=torch.float32) * scale
-
-
-def _ratio(err, bound):
-    """worst err / bound; a zero bound asks for a zero error"""
-    err, bound = np.asarray(err, dtype=np.float64), np.asarray(bound, dtype=np.float64)
-    r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, np.inf))
-    return float(r.max()) if r.size else 0.0
 
 
 def _bits(a):
@@ -107,12 +99,6 @@ def test_prep_f32_nchw(ops, H, W, B, std):
 
 
 # --------------------------------------------------------------------------------------------------------------- regression prediction heads
-def _normalize_bounds(d, E, n):
-    """F.normalize of the 2-vector d (fp64, (..., 2)) whose components carry absolute errors E: with g = d / n, d g_0 = g_1 (g_1 dd_0 - g_0 dd_1) / n, so
-    |d g_i| <= |dd|_2 / n <= hypot(E_0, E_1) / n -- the dot products' error divided by the fp64 norm -- plus 4 u for the fp32 squares, sum, square root and division."""
-    return np.hypot(E[..., 0], E[..., 1])[..., None] / n[..., None] + 4 * U
-
-
 def _heads_reference(tg, tl, wg, bg, wl, bl):
     """fp64 dot products, their summation bounds 32 u sum_k |a_k w_k|, and the reference outputs"""
     tg, tl, wg, bg, wl, bl = (np.asarray(t, dtype=np.float64) for t in (tg, tl, wg, bg, wl, bl))
@@ -568,14 +554,6 @@ def head_case():
     b = _rand((32,), 1002, 0.1)
     fmap = F.relu(F.conv2d(x.double().permute(0, 3, 1, 2), w.double(), b.double(), padding=1)).permute(0, 2, 3, 1).reshape(HB, HH * HWID, 32).numpy()
     return {"x": x, "xd": x.cuda(), "w": w, "b": b, "map": fmap, "map_err": 2e-5 * (1.0 + np.abs(fmap))}  # the bound of tests/test_gpu_ops.py::test_conv2d_all_tiles
-
-
-def _head_bounds(case, hw, hb):
-    """fp64 head outputs on the fp64 map and the bounds: the map's error through |w| (ReLU is 1-Lipschitz) plus the head's own summation, then as for pred_regression"""
-    hw, hb = np.asarray(hw, dtype=np.float64), np.asarray(hb, dtype=np.float64)
-    raw = case["map"] @ hw.T + hb                                                   # (B, HW, nout)
-    E = case["map_err"] @ np.abs(hw).T + 32 * U * (np.abs(case["map"]) @ np.abs(hw).T)
-    return raw, E
 
 
 def test_fused_head_tile_list():

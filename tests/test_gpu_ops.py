@@ -822,3 +822,32 @@ def test_conv2d_winograd_tile(ops, case, tile_name):
     # no bias
     got2 = ops.conv2d(xd, w, None, pad=1, tile=tw, splitk=False).double().cpu()
     assert ((got2 - _ref_conv(x, w, None, 1, 1)).abs() / scale).max().item() <= 4 * ed + 2.0 ** -20, name
+
+
+def test_every_conv_tile_is_run_by_a_case_that_names_it(ops):
+    """pf_op_conv2d replaces a named tile that cannot run the shape by the cost model's (fp32 operands), so test_conv2d_all_tiles alone cannot say which tiles it has run.
+    pf_op_conv2d_g_tile_usable (groups = 1, ups = 0: the same conv_tile_usable on the same operand set, under either parity scheme) can: over CONV_CASES, WINO_CASES and
+    the plain launches of tests/test_gpu_conv_forms.py, each with the tiles its test names, every tile runs at least once.  CONV_CASES does not count for the Winograd
+    tiles: test_conv2d_all_tiles leaves the split-K rule on, under which a Winograd tile is replaced (test_conv2d_winograd_tile says so and switches it off).  Cases
+    outside the query's precondition (C1 or C2 no multiple of 32: the stems, 96 channels) count as not run."""
+    from tests.conv_form_cases import plain_conv_cases
+
+    names = ops.conv_tiles()
+    wino = [n for n in names if n.startswith("wino")]
+    cases = [(c, [n for n in names if n not in wino]) for c in CONV_CASES] + [((n, B, H, W, Cin, 0, Cout, 3, 1, 1), wino) for n, B, H, W, Cin, Cout in WINO_CASES] + plain_conv_cases(ops)
+    ran = {n: [] for n in names}
+    for (cname, B, H, W, C1, C2, Cout, K, stride, pad), named in cases:
+        usable = set()
+        for precision in (0, 3):
+            usable |= set(ops.conv2d_g_tiles(B, H, W, C1, Cout, K, stride=stride, pad=pad, C2=C2, precision=precision))
+        for n in named:
+            if names.index(n) in usable:
+                ran[n].append(cname)
+    width = max(len(n) for n in names)
+    print(f"[conv tile coverage] {len(cases)} cases; per tile the cases that name it and can run on it ('#' = runs, '.' = replaced or not named)")
+    for n in names:
+        row = "".join("#" if c[0][0] in ran[n] and n in c[1] else "." for c in cases)
+        print(f"[conv tile coverage] {n:<{width}} {len(ran[n]):3d} {row}")
+    own = {c[0] for c in CONV_CASES} | {c[0] for c in WINO_CASES}   # the assertion below is met by the cases of tests/test_gpu_conv_forms.py alone; what this file runs:
+    print(f"[conv tile coverage] run by a case of this file: {[n for n in names if own & set(ran[n])]}; by the conv-forms cases only: {[n for n in names if ran[n] and not own & set(ran[n])]}")
+    assert all(ran[n] for n in names), f"tiles no case runs: {[n for n in names if not ran[n]]}"

@@ -1,6 +1,7 @@
 """CPU-only tests of the host side: config / zoo, checkpoint schema and strict validation, synthetic
 checkpoint determinism, C-ABI library loading + symbol export, weight-fold algebra, shard logic."""
 import ctypes
+import math
 import os
 import re
 
@@ -698,3 +699,88 @@ def test_fused_head_tile_list_is_host_logic():
     for args in ((0, 17, 24, 64, 1, 1), (2, 17, 24, 48, 1, 1), (2, 17, 24, 64, 3, 1), (2, 17, 24, 64, 1, 0), (2, 17, 24, 64, 1, 3), (81, 320, 320, 256, 1, 1)):
         assert lib.pf_op_conv2d_head_tile_usable(*args, ok) == 0, args
     assert lib.pf_op_conv2d_head_tile_usable(2, 17, 24, 64, 1, 1, -1) == 0 and lib.pf_op_conv2d_head_tile_usable(2, 17, 24, 64, 1, 1, len(names)) == 0
+
+
+def test_conv2d_g_tile_lists_are_host_logic():
+    """pf_op_conv2d_g_tile_usable needs no device: tests/test_gpu_conv_forms.py reads its tile lists at collection.  The fused x2 up-sampling runs on the 4-wave halo
+    tiles of the split-f16 scheme only; two groups run wherever one does; a bias table runs everywhere but on the Winograd tiles; a fused head on the BN = 32 split
+    tiles; and every precondition of pf_op_conv2d_g that the shape alone decides answers 0 for every tile."""
+    from perspectivefields_amd import ops
+
+    names = ops.conv_tiles()
+    tiles = lambda **form: [names[t] for t in ops.conv2d_g_tiles(**form)]
+    linear = lambda n: n.startswith("sb") and not n.startswith("sbh")
+    halo = lambda n: n.startswith("sbh")
+    ups = dict(B=2, H=6, W=10, C1=64, Cout=64, K=3, pad=1, ups=True)
+    ups_t = tiles(**ups)
+    assert all(halo(n) for n in ups_t) and any(n.startswith("sbh128x") for n in ups_t) and {"sbh256x32", "sbh256x64"} <= set(ups_t) and "sbh256x64w8" not in ups_t, ups_t
+    assert tiles(**dict(ups, C2=32)) == ups_t == tiles(**dict(ups, groups=2)) == tiles(**dict(ups, has_table=True))
+    ups_head = tiles(**dict(ups, Cout=32, act=1, head_kind=1))
+    assert ups_head and set(ups_head) <= set(ups_t) and all(n.endswith("x32") for n in ups_head) and ups_head == tiles(**dict(ups, Cout=32, act=1, head_kind=2)), ups_head
+    for bad in (dict(H=7), dict(W=9), dict(precision=3), dict(K=1, pad=0), dict(stride=2), dict(C1=48), dict(C2=16), dict(groups=3), dict(groups=0), dict(head_kind=1),
+                dict(act=3), dict(precision=1), dict(B=0)):
+        assert tiles(**dict(ups, **bad)) == [], bad
+    plain = dict(B=1, H=10, W=10, C1=64, Cout=64, K=3, pad=1)
+    plain_t = tiles(**plain)
+    assert "128x128p" in plain_t and any(linear(n) for n in plain_t) and set(ups_t) <= set(plain_t) and {"wino256x64c", "wino256x64d"} <= set(plain_t), plain_t
+    assert tiles(**dict(plain, groups=2)) == plain_t
+    exact = tiles(**dict(plain, precision=3))   # the exact bf16 split: no Winograd, no split-f16-only halo tile
+    assert set(exact) < set(plain_t) and "128x128p" in exact and any(linear(n) for n in exact) and any(halo(n) for n in exact), exact
+    assert not any(n.startswith("wino") or n in ("sbh256x32", "sbh256x64") for n in exact), exact
+    assert tiles(**dict(plain, has_table=True)) == [n for n in plain_t if not n.startswith("wino")]
+    for H, W in ((1, 10), (10, 1)):
+        assert tiles(**dict(plain, H=H, W=W)) and tiles(**dict(plain, H=H, W=W, has_table=True)) == []
+    one = tiles(**dict(plain, K=1, pad=0, Cout=96, groups=2))
+    assert "128x128p" in one and any(linear(n) for n in one) and not any(halo(n) or n.startswith("wino") for n in one), one
+    heads = tiles(**dict(plain, Cout=32, act=1, groups=2, head_kind=1))
+    assert any(linear(n) for n in heads) and any(halo(n) for n in heads) and all(n.endswith(("x32", "x32f2")) for n in heads), heads
+    assert "128x32p" not in heads and tiles(**dict(plain, Cout=64, head_kind=1)) == []
+    lib = ops.load_library()
+    args = (1, 10, 10, 64, 0, 64, 3, 3, 1, 1, 0, 2, 0, 0, 0, 0)
+    assert lib.pf_op_conv2d_g_tile_usable(*args, -1) == 0 and lib.pf_op_conv2d_g_tile_usable(*args, len(names)) == 0 and lib.pf_op_conv2d_g_tile_usable(*args, 0) == 1
+
+
+def test_conv2d_g_refuses_a_tile_before_any_device_work():
+    """pf_op_conv2d_g decides the tile on the operand set of the usability query, before it asks for a device or uploads a weight: a named tile that cannot run the form,
+    and a form that no tile runs, are PF_ERR_ARG with that reason -- here too, where no call reaches a device.  Host buffers stand in for the device tensors: a refused
+    call reads none of them (only refused calls are made)."""
+    from perspectivefields_amd import ops
+
+    PF_ERR_ARG = -1  # include/pf_hip.h
+    lib = ops.load_library()
+    names = ops.conv_tiles()
+    B, H, W, C, Cout = 1, 6, 6, 64, 64
+    x, y = np.zeros(B * H * W * C + 4, np.float32), np.zeros(B * H * W * Cout + 4, np.float32)
+    w, tab = np.zeros((Cout, C, 3, 3), np.float32), np.zeros((9, Cout), np.float32)
+    al = lambda a: a.ctypes.data + (-a.ctypes.data) % 16
+    ptr = lambda v: (ctypes.c_void_p * 1)(v)
+    used = ctypes.c_int(0)
+
+    def call(tile, K=3, pad=1, stride=1, ups=0, rows=1):
+        rc = lib.pf_op_conv2d_g(0, 1, ptr(al(x)), None, B, H, W, C, 0, ptr(w.ctypes.data), ptr(tab.ctypes.data), (ctypes.c_int * 1)(rows), Cout, K, K, stride, pad, 0,
+                                None, None, 0, ups, ptr(al(y)), (ctypes.c_int * 1)(0), None, None, None, None, tile, 0, -1, ctypes.byref(used), None)
+        return rc, (lib.pf_last_error(None) or b"").decode()
+
+    for tile, kw in ((names.index("128x128p"), dict(ups=1)), (names.index("sb128x128"), dict(ups=1)), (names.index("sbh256x64w8"), dict(ups=1)),
+                     (names.index("wino256x64c"), dict(rows=9)), (names.index("sbh128x64"), dict(K=1, pad=0))):
+        rc, msg = call(tile, **kw)
+        assert rc == PF_ERR_ARG and f"({names[tile]}) cannot run this form" in msg, (names[tile], kw, rc, msg)
+    for kw in (dict(ups=1, K=1, pad=0), dict(ups=1, stride=2)):
+        rc, msg = call(-1, **kw)
+        assert rc == PF_ERR_ARG and "no tile runs this form" in msg, (kw, rc, msg)
+
+
+def test_a_nan_output_cannot_pass_the_kernel_bounds():
+    """the accumulation of the kernel-level GPU tests (tests/kernel_bounds.py): an output element that is NaN -- unwritten under ops.checked_outputs() -- gives a NaN
+    ratio, the running worst keeps it whatever comes before or after, and `worst <= 1.0` is then false"""
+    from tests.kernel_bounds import _ratio, _worse
+
+    nan = float("nan")
+    r = _ratio(np.abs(np.array([0.1, nan]) - np.array([0.1, 0.2])), np.array([1.0, 1.0]))
+    assert math.isnan(r)
+    for seq in ((r, 0.5), (0.5, r), (0.2, r, 0.9), (r,)):
+        worst = 0.0
+        for v in seq:
+            worst = _worse(worst, v)
+        assert math.isnan(worst) and not worst <= 1.0, seq
+    assert math.isnan(_worse(0.0, 0.3, nan, 0.4)) and _worse(0.0, 0.3, 0.7, 0.4) == 0.7 and _worse(0.5, 0.3) == 0.5 and _worse(0.0, float("inf")) == float("inf")
