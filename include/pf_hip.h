@@ -694,6 +694,61 @@ int pf_pano_to_fisheye(int device, int n_pano, const void* const* h_pano, const 
 int pf_fisheye_fields(int device, int kind, int batch, const float* d_lens /*[batch][2][12]*/, int H, int W, float* d_up /*[batch][2][H][W]*/,
                       float* d_lat /*[batch][H][W]*/, void* stream);
 
+/* The other direction: a fisheye lens fitted to perspective fields, the batched per-image Levenberg-Marquardt fit of pf_fit_camera over the lens
+ * model above (fit_camera_fisheye.hip).  theta = (roll r, pitch p, f, cx, cy, k1, k2), NTH = 7: roll and pitch in RADIANS,
+ * the relative intrinsics of the other fits, F = f*H, Cx = (cx + 1/2)*W, Cy = (cy + 1/2)*H, and the first two Kannala-Brandt coefficients;
+ * k3 = k4 = 0.  The projection kind is one integer per call (PF_FISHEYE_*).  Yaw, `band` and a second lens do not enter.
+ * THE MODEL per pixel, at the pixel centre (a, b) = (col + 1/2, row + 1/2) for BOTH labels (there is no linspace grid):
+ *   1 radius    dx = a - Cx, dy = b - Cy, r = hypot(dx, dy), rho = r / F; the equisolid kind needs rho < 2
+ *   2 theta     theta_d = rho | 2 asin(rho / 2) | 2 atan(rho / 2).  theta = theta_d if k1 = k2 = 0 exactly; otherwise from min(theta_d, theta_max)
+ *               exactly PF_FISHEYE_NEWTON_STEPS steps theta <- clamp(theta - (P(theta) - theta_d) / P'(theta), 0, theta_max), in plain floats
+ *   3 domain    the pixel HAS A MODEL VALUE iff all of these hold (positive comparisons: a NaN has none):
+ *               r - PF_FISHFIT_R_MIN > 0 (the polar form has no derivative at the centre; at most one pixel);
+ *               theta_max - theta > 0, theta_max the call's argument in (0, pi): the widest half field of view the caller allows;
+ *               theta > 0 (a clamped iteration may end on the axis when theta_d is within the root tolerance: m / sin theta has no value there);
+ *               with a polynomial, P'(theta) >= PF_FISHFIT_SLOPE_MIN and |P(theta) - theta_d| <= PF_FISHFIT_ROOT_TOL.
+ *               That is: the Newton iteration found an interior root on a rising branch.  It is NOT r < r_max(theta_max), which means nothing for
+ *               a trial polynomial that is not monotone.  A pixel without a model value has weight 0 and is not counted in VALID_PIXELS.
+ *   4 d theta   from the implicit function, not through the Newton loop: d theta = (d theta_d - theta^3 d k1 - theta^5 d k2) / P'(theta)
+ *   5 labels    pf_pano_to_fisheye's: latitude = -atan2(W.y, hypot(W.x, W.z)) in degrees, W = R X; up from g, e_theta, e_phi, m = rho,
+ *               m' = rho'(theta_d) P'(theta).  Where |t|^2 < PF_PANO_UP_MIN_T2 the two up rows have weight 0; the latitude row stays.
+ * Residuals, loss, weights, damping, accept / reject and stopping rule: as pf_fit_camera.  Clamps: |pitch| <= 89.9 deg, f >= 1e-3, roll wrapped
+ * into [-pi, pi], k1 and k2 in [-0.5, 0.5].  FREE SETS: (r, p, f); with free_pp also cx, cy; with poly also k1, k2; all seven with both.  Held
+ * entries keep their start values, so a calibrated k1, k2 can be held while orientation and focal length are fitted.
+ * Start: d_init = DEVICE [B][7] theta, or NULL: roll and pitch from the 4 x 4 centre pixels (at the circle centre up = (-sin r, -cos r) and
+ * lat = p for every kind), cx = cy = k1 = k2 = 0, and f the best of the 16 candidates f = 0.5 / rho(h_c), h_c = (20 + 7 c) degrees the half field
+ * of view over half the height.  Pixels outside the image circle are expected as NaN in the input.  An image without a pixel that has finite input
+ * and a model value, or with a non-finite entry in its d_init row, ends with CONVERGED 0, VALID_PIXELS 0 and its start parameters.
+ * d_out = DEVICE [B][PF_FISHFIT_COLS] fp32: the thirteen columns of pf_fit_camera in the same order, then k1, k2.  VFOV and GENERAL_VFOV keep
+ * their formulas in f, cx, cy: for a fisheye lens they describe nothing.
+ * Argument errors return PF_ERR_ARG before any device work with a message that begins with "pf_fit_fisheye: ", checked in this order: an unknown
+ * `kind`; theta_max outside (0, pi) or not finite; then pf_fit_camera's checks (and poly other than 0 / 1 with free_pp).  Sizes, pointers,
+ * launches (max_iter + 1 pairs per 32 images on `stream`, no host synchronisation) and determinism (an image's bits do not depend on its batch)
+ * as pf_fit_camera; workspace pf_fit_fisheye_workspace_bytes (0 for batch <= 0 or a size below 8). */
+#define PF_FISHFIT_R_MIN 1e-3f     /* pixels */
+#define PF_FISHFIT_SLOPE_MIN 1e-2f
+#define PF_FISHFIT_ROOT_TOL 4e-6f  /* 16 x the float32 Newton residual of the test lenses (2.4e-7), rounded up */
+#define PF_FISHFIT_COL_ROLL 0
+#define PF_FISHFIT_COL_PITCH 1
+#define PF_FISHFIT_COL_VFOV 2
+#define PF_FISHFIT_COL_REL_FOCAL 3
+#define PF_FISHFIT_COL_GENERAL_VFOV 4
+#define PF_FISHFIT_COL_REL_CX 5
+#define PF_FISHFIT_COL_REL_CY 6
+#define PF_FISHFIT_COL_RMS_UP 7
+#define PF_FISHFIT_COL_RMS_LAT 8
+#define PF_FISHFIT_COL_COST 9
+#define PF_FISHFIT_COL_ITERATIONS 10
+#define PF_FISHFIT_COL_CONVERGED 11
+#define PF_FISHFIT_COL_VALID_PIXELS 12 /* pixels with finite input and a model value */
+#define PF_FISHFIT_COL_K1 13
+#define PF_FISHFIT_COL_K2 14
+#define PF_FISHFIT_COLS 15
+size_t pf_fit_fisheye_workspace_bytes(int batch, const int32_t* h_hw);
+int pf_fit_fisheye(int device, int kind, int batch, const int32_t* h_hw, const float* const* h_up, const float* const* h_lat,
+                   const float* d_init /* NULL or [B][7] */, int free_pp, int poly, float theta_max, int loss, float huber_delta_deg, float w_up,
+                   float w_lat, int max_iter, float* d_out /* [B][PF_FISHFIT_COLS] */, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* The relative yaw of camera views of one centre, from the pictures: for ordered pairs (a, b) of views and a list of candidate turns, the moments of
  * the two luminance images on their overlap, from which the zero-mean normalised cross-correlation follows (yaw_align.hip).
  * The fields give roll, pitch and intrinsics of a view but not the direction it faces; with those known, two views of one centre differ by a single

@@ -15,11 +15,12 @@ panorama composition, on one host skeleton), yaw (yaw alignment, gravity from vi
 __all__ = ["PerspectiveFields", "model_zoo", "fields_from_params", "fit_camera_params", "fit_camera_shared", "crop_panorama", "reproject_image", "compose_panorama", "rotate_panorama", "panorama_fields", "gravity_from_views", "crop_cubemap", "cubemap_to_panorama", "panorama_to_cubemap", "cubemap_face_cameras", "cubemap_to_image", "cubemap_from_image", "fisheye_lens", "dual_fisheye_lenses", "crop_fisheye", "fisheye_to_panorama", "yaw_scores", "align_yaw", "yaw_tree", "placement_scores", "placement_search", "transform_fields", "composite_objects", "draw_perspective_fields", "draw_camera", "field_errors", "FieldErrorAccumulator"]
 
 
-# public name -> the module that defines it.  panorama_to_fisheye and fisheye_fields are public through this table alone: __all__ keeps its 32 names
+# public name -> the module that defines it.  panorama_to_fisheye, fisheye_fields, fit_fisheye_lens and fisheye_lens_from_fit are public through this table
+# alone: __all__ keeps its 32 names
 _HOME = {
     "PerspectiveFields": "perspectivefields", "model_zoo": "config",
     "fields_from_params": "fields",
-    "fit_camera_params": "camera_fit", "fit_camera_shared": "camera_fit",
+    "fit_camera_params": "camera_fit", "fit_camera_shared": "camera_fit", "fit_fisheye_lens": "camera_fit", "fisheye_lens_from_fit": "camera_fit",
     "field_errors": "field_metrics", "FieldErrorAccumulator": "field_metrics",
     "placement_scores": "placement", "placement_search": "placement", "transform_fields": "placement", "composite_objects": "placement",
     "draw_perspective_fields": "draw", "draw_camera": "draw",

@@ -51,4 +51,30 @@ __device__ __forceinline__ float fisheye_rho_slope(int kind, float td) {
   return kind == PF_FISHEYE_EQUISOLID ? c : 1.f / (c * c);
 }
 
+// The same functions over the dual numbers T of fit_dual.h (the lens fit, fit_camera_fisheye.hip), with k3 = k4 = 0 and the kind at
+// compile time.  Templates, so a unit that does not instantiate them carries nothing of them; dsincos, dasin, datan and recip are found where T is.
+template <class T>
+__device__ __forceinline__ T fisheye_poly_slope(const T& t, const T& k1, const T& k2) {
+  const T t2 = t * t;
+  return t2 * (k1 * 3.f + t2 * (k2 * 5.f)) + 1.f;
+}
+
+// the caller has made sure that rho < 2 for the equisolid kind
+template <int KIND, class T>
+__device__ __forceinline__ T fisheye_rho_inverse(const T& rho) {
+  if constexpr (KIND == PF_FISHEYE_EQUIDISTANT) return rho;
+  else if constexpr (KIND == PF_FISHEYE_EQUISOLID) return dasin(rho * 0.5f) * 2.f;
+  else return datan(rho * 0.5f) * 2.f;
+}
+
+// rho'(td) of the two kinds where it is not 1
+template <int KIND, class T>
+__device__ __forceinline__ T fisheye_rho_slope(const T& td) {
+  static_assert(KIND == PF_FISHEYE_EQUISOLID || KIND == PF_FISHEYE_STEREOGRAPHIC, "rho' = 1 for the equidistant kind");
+  T s, c;
+  dsincos(td * 0.5f, &s, &c);
+  if constexpr (KIND == PF_FISHEYE_EQUISOLID) return c;
+  else return recip(c * c);
+}
+
 }  // namespace pf

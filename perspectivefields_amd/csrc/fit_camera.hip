@@ -114,6 +114,8 @@ struct PinholeFit {
     acc[R::CNT] += 1.f;
   }
 
+  static __device__ __forceinline__ float start_focal(int c) { return start_focal_vfov(c); }
+
   static __device__ __forceinline__ CamModel<float> start_model(const double* th, float f, int H, int W) {
     return CamModel<float>((float)th[0], (float)th[1], f, 0.f, 0.f, H, W);
   }

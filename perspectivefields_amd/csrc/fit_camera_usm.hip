@@ -18,18 +18,6 @@ namespace pf {
 
 namespace {
 
-// A value that every lane of the block computed from the same inputs: said so, it lives in a scalar register.  The model's
-// parameter-only quantities are 17 dual numbers; in vector registers they alone would take most of the budget of Dual<6>.
-__device__ __forceinline__ float uni(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-template <int N>
-__device__ __forceinline__ Dual<N> uni(const Dual<N>& a) {
-  Dual<N> r;
-  r.v = uni(a.v);
-#pragma unroll
-  for (int k = 0; k < N; ++k) r.d[k] = uni(a.d[k]);
-  return r;
-}
-
 // ---------------------------------------------------------------- the model, ONE source for T = float and T = Dual<N>
 // The constructor does everything that depends on the parameters only (trig, g, the rows of R, 1 / F, the affine coefficients
 // of x and y on both grids).  A pixel costs two unprojections (one sqrt and one reciprocal each), one rsqrt, one sqrt and
@@ -107,23 +95,6 @@ struct UsmModel {
 
 constexpr double kXiMin = -0.5, kXiMax = 2.0;
 
-// one residual row into the sums: Jacobian row m.d * scale (0 where the model is undefined), residual r, weight w
-template <int NP>
-__device__ __forceinline__ void add_row(float* acc, const Dual<NP>& m, bool ok, float scale, float w, float r) {
-  using R = Rec<NP>;
-  float j[NP];
-#pragma unroll
-  for (int k = 0; k < NP; ++k) j[k] = ok ? m.d[k] * scale : 0.f;
-  int t = 0;
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    const float a = w * j[i];
-#pragma unroll
-    for (int jj = i; jj < NP; ++jj, ++t) acc[t] = fmaf(a, j[jj], acc[t]);
-    acc[R::G + i] = fmaf(a, r, acc[R::G + i]);
-  }
-}
-
 }  // namespace
 
 struct UsmFit {
@@ -189,6 +160,8 @@ struct UsmFit {
     }
     acc[R::CNT] += 1.f;
   }
+
+  static __device__ __forceinline__ float start_focal(int c) { return start_focal_vfov(c); }
 
   // The centre ray is (0, 0, 1) for every xi, so the start of the pinhole fit holds here too; its candidates are searched at xi = 0.
   static __device__ __forceinline__ UsmModel<float> start_model(const double* th, float f, int H, int W) {

@@ -1,5 +1,5 @@
-// Shared pieces of the camera fits (fit_camera.hip: pinhole, fit_camera_usm.hip: Unified Spherical Model): forward-mode dual
-// numbers, the Huber / L2 loss and the wave reduction.  Everything is __forceinline__ and internal to the including unit.
+// Shared pieces of the camera fits (fit_camera.hip: pinhole, fit_camera_usm.hip: Unified Spherical Model, fit_camera_fisheye.hip: fisheye
+// lenses): forward-mode dual numbers, the wave-uniform mark, the Huber / L2 loss and the wave reduction.  Everything is __forceinline__ and internal to the including unit.
 #pragma once
 
 #include <math.h>
@@ -130,6 +130,26 @@ __device__ __forceinline__ Dual<N> datan2(const Dual<N>& y, const Dual<N>& x) {
 }
 __device__ __forceinline__ float datan2(float y, float x) { return atan2f(y, x); }
 template <int N>
+__device__ __forceinline__ Dual<N> dasin(const Dual<N>& a) {
+  Dual<N> r;
+  r.v = asinf(a.v);
+  const float g = 1.0f / sqrtf(1.0f - a.v * a.v);
+#pragma unroll
+  for (int k = 0; k < N; ++k) r.d[k] = a.d[k] * g;
+  return r;
+}
+__device__ __forceinline__ float dasin(float a) { return asinf(a); }
+template <int N>
+__device__ __forceinline__ Dual<N> datan(const Dual<N>& a) {
+  Dual<N> r;
+  r.v = atanf(a.v);
+  const float g = 1.0f / fmaf(a.v, a.v, 1.0f);
+#pragma unroll
+  for (int k = 0; k < N; ++k) r.d[k] = a.d[k] * g;
+  return r;
+}
+__device__ __forceinline__ float datan(float a) { return atanf(a); }
+template <int N>
 __device__ __forceinline__ void dsincos(const Dual<N>& a, Dual<N>* s, Dual<N>* c) {
   float sv, cv;
   sincosf(a.v, &sv, &cv);
@@ -145,6 +165,18 @@ __device__ __forceinline__ void dsincos(float a, float* s, float* c) { sincosf(a
 __device__ __forceinline__ float val(float a) { return a; }
 template <int N>
 __device__ __forceinline__ float val(const Dual<N>& a) { return a.v; }
+
+// A value that every lane of the block computed from the same inputs: said so, it lives in a scalar register.  The parameter-only
+// quantities of the USM and fisheye models are 13 to 17 dual numbers; in vector registers they alone would take most of the budget of Dual<6>.
+__device__ __forceinline__ float uni(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+template <int N>
+__device__ __forceinline__ Dual<N> uni(const Dual<N>& a) {
+  Dual<N> r;
+  r.v = uni(a.v);
+#pragma unroll
+  for (int k = 0; k < N; ++k) r.d[k] = uni(a.d[k]);
+  return r;
+}
 
 // Huber by IRLS: weight of a residual of norm r, and rho(r)
 __device__ __forceinline__ void loss_of(float r, int huber, float delta, float* w, float* rho) {

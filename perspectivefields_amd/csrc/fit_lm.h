@@ -1,5 +1,5 @@
-// The Levenberg-Marquardt driver of the camera fits (fit_camera.hip: pinhole, fit_camera_usm.hip: Unified Spherical Model; DESIGN.md
-// sections 10, 14 and 15): everything that does not depend on the camera model, once.
+// The Levenberg-Marquardt driver of the camera fits (fit_camera.hip: pinhole, fit_camera_usm.hip: Unified Spherical Model,
+// fit_camera_fisheye.hip: fisheye lenses; DESIGN.md sections 10, 14, 15 and 37): everything that does not depend on the camera model, once.
 //   fit_init_kernel<Fit>        one wave per image: start parameters (or a copy of the caller's), state reset
 //   fit_accum_kernel<Fit, NP>   grid (blocks per image) x (images): model + Jacobian per pixel by forward-mode dual numbers,
 //                               upper triangle of J^T W J, J^T W r, cost and the rms sums per block -> one partial record per block
@@ -18,6 +18,7 @@
 //   clamp_theta(th)             theta back into the model's range
 //   model_at<NP>(th, H, W)      the model over Dual<NP>: derivative k of free parameter k, constants for the held parameters
 //   accum_pixel<NP>(m, col, row, pux, puy, plat, prm, acc)   one pixel into the block's fp32 sums, laid out as Rec<NP>
+//   start_focal(c)              the focal length of candidate c = 0 ... 15 of the start search
 //   start_model(th, f, H, W)    the model over float at (th[0], th[1], f) and zeros: a candidate of the start search
 //   start_cost(m, col, row, pux, puy, plat, prm, cost)       one pixel's cost at a candidate, added to cost term by term
 // The per-pixel accumulation stays with the model on purpose: the two models add their residual rows in different fp32 orders.
@@ -63,6 +64,23 @@ struct St {
   static_assert(Rec<Fit::NTH>::NV <= Fit::REC, "record too small");
 };
 
+// one residual row into a block's sums (the models that add their rows one after the other: USM, fisheye): Jacobian row m.d * scale (0 where the model is undefined), residual r, weight w
+template <int NP>
+__device__ __forceinline__ void add_row(float* acc, const Dual<NP>& m, bool ok, float scale, float w, float r) {
+  using R = Rec<NP>;
+  float j[NP];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) j[k] = ok ? m.d[k] * scale : 0.f;
+  int t = 0;
+#pragma unroll
+  for (int i = 0; i < NP; ++i) {
+    const float a = w * j[i];
+#pragma unroll
+    for (int jj = i; jj < NP; ++jj, ++t) acc[t] = fmaf(a, j[jj], acc[t]);
+    acc[R::G + i] = fmaf(a, r, acc[R::G + i]);
+  }
+}
+
 constexpr double kPi = 3.14159265358979323846;
 constexpr double kPitchMax = 89.9 * kPi / 180.0, kFocalMin = 1e-3;
 
@@ -97,14 +115,25 @@ __device__ void write_out(float* o, const double* st) {
   o[PF_FIT_COL_CONVERGED] = st[S::CONV] == 1.0 ? 1.f : 0.f;
   o[PF_FIT_COL_VALID_PIXELS] = (float)n;
   if constexpr (Fit::NTH == 6) o[PF_USMFIT_COL_XI] = (float)th[5];
+  if constexpr (Fit::NTH == 7) {
+    o[PF_FISHFIT_COL_K1] = (float)th[5];
+    o[PF_FISHFIT_COL_K2] = (float)th[6];
+    if (!(n > 0.0)) o[PF_FISHFIT_COL_CONVERGED] = 0.f;  // a cost of 0 over no pixel at all met no tolerance
+  }
+}
+
+// candidate c of 16 of the start search of a camera with a vertical field of view: vFoV in [15, 150] deg
+__device__ __forceinline__ float start_focal_vfov(int c) {
+  const double vfov = (15.0 + 9.0 * c) * (kPi / 180.0);
+  return (float)(0.5 / tan(0.5 * vfov));
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------- init: one wave per image
 // roll from the up vector and pitch from the latitude at the image centre (there u = (-sin r, -cos r) and lat = pitch
-// whatever the other parameters), averaged over the 4 x 4 pixels around it; f from the best of 16 vFoV candidates in
-// [15, 150] deg by the cost on a 32 x 32 subsample; zeros beyond.  With fb.init: the caller's [NTH] parameters instead.
+// whatever the other parameters), averaged over the 4 x 4 pixels around it; f from the best of the model's 16 candidates
+// (Fit::start_focal) by the cost on a 32 x 32 subsample; zeros beyond.  With fb.init: the caller's [NTH] parameters instead.
 template <class Fit>
 __global__ __launch_bounds__(64) void fit_init_kernel(const FitBatch fb, const FitParams prm) {
   using S = St<Fit>;
@@ -149,8 +178,7 @@ __global__ __launch_bounds__(64) void fit_init_kernel(const FitBatch fb, const F
     }
     float best = INFINITY;
     for (int c = 0; c < 16; ++c) {
-      const double vfov = (15.0 + 9.0 * c) * (kPi / 180.0);
-      const float f = (float)(0.5 / tan(0.5 * vfov));
+      const float f = Fit::start_focal(c);
       const auto m = Fit::start_model(th, f, H, W);
       float cost = 0.f;
 #pragma unroll

@@ -1018,8 +1018,8 @@ int pf_composite(int device, int n_bg, const void* const* bg, const int32_t* bg_
   return PF_OK;
 }
 
-// workspace of pf_fit_camera / pf_fit_camera_usm: per-image LM state, then every image's partial records, each region 256-byte aligned.
-// The two fits differ in their state, record, start and output row sizes and in their kernels only.
+// workspace of pf_fit_camera / pf_fit_camera_usm / pf_fit_fisheye: per-image LM state, then every image's partial records, each region 256-byte aligned.
+// The fits differ in their state, record, start and output row sizes and in their kernels only.
 struct FitKind {
   const char* name;
   int state, rec, ntheta, cols;
@@ -1028,6 +1028,22 @@ struct FitKind {
 };
 static const FitKind kFitPinhole{"pf_fit_camera", FIT_STATE, FIT_REC, 5, PF_FIT_COLS, launch_fit_init<PinholeFit>, launch_fit_iteration<PinholeFit>};
 static const FitKind kFitUsm{"pf_fit_camera_usm", USMFIT_STATE, USMFIT_REC, 6, PF_USMFIT_COLS, launch_fit_init<UsmFit>, launch_fit_iteration<UsmFit>};
+// the lens fit: one per projection kind, without and with the polynomial's coefficients free
+#define PF_FISHFIT_KIND(KIND, POLY) \
+  FitKind{"pf_fit_fisheye", FISHFIT_STATE, FISHFIT_REC, 7, PF_FISHFIT_COLS, launch_fit_init<FisheyeFit<KIND, POLY>>, launch_fit_iteration<FisheyeFit<KIND, POLY>>}
+static const FitKind kFitFisheye[3][2] = {{PF_FISHFIT_KIND(PF_FISHEYE_EQUIDISTANT, false), PF_FISHFIT_KIND(PF_FISHEYE_EQUIDISTANT, true)},
+                                          {PF_FISHFIT_KIND(PF_FISHEYE_EQUISOLID, false), PF_FISHFIT_KIND(PF_FISHEYE_EQUISOLID, true)},
+                                          {PF_FISHFIT_KIND(PF_FISHEYE_STEREOGRAPHIC, false), PF_FISHFIT_KIND(PF_FISHEYE_STEREOGRAPHIC, true)}};
+#undef PF_FISHFIT_KIND
+static_assert(PF_FISHEYE_EQUIDISTANT == 0 && PF_FISHEYE_EQUISOLID == 1 && PF_FISHEYE_STEREOGRAPHIC == 2, "kFitFisheye is indexed by the kind");
+static_assert(PF_FISHFIT_COL_ROLL == PF_FIT_COL_ROLL && PF_FISHFIT_COL_PITCH == PF_FIT_COL_PITCH && PF_FISHFIT_COL_VFOV == PF_FIT_COL_VFOV &&
+                  PF_FISHFIT_COL_REL_FOCAL == PF_FIT_COL_REL_FOCAL && PF_FISHFIT_COL_GENERAL_VFOV == PF_FIT_COL_GENERAL_VFOV &&
+                  PF_FISHFIT_COL_REL_CX == PF_FIT_COL_REL_CX && PF_FISHFIT_COL_REL_CY == PF_FIT_COL_REL_CY && PF_FISHFIT_COL_RMS_UP == PF_FIT_COL_RMS_UP &&
+                  PF_FISHFIT_COL_RMS_LAT == PF_FIT_COL_RMS_LAT && PF_FISHFIT_COL_COST == PF_FIT_COL_COST &&
+                  PF_FISHFIT_COL_ITERATIONS == PF_FIT_COL_ITERATIONS && PF_FISHFIT_COL_CONVERGED == PF_FIT_COL_CONVERGED &&
+                  PF_FISHFIT_COL_VALID_PIXELS == PF_FIT_COL_VALID_PIXELS && PF_FISHFIT_COL_K1 == PF_FIT_COLS && PF_FISHFIT_COL_K2 == PF_FIT_COLS + 1 &&
+                  PF_FISHFIT_COLS == PF_FIT_COLS + 2,
+              "the lens fit's output row is the pinhole row, then k1, k2");
 static size_t fit_state_bytes(const FitKind& fk, int B) { return ((size_t)B * fk.state * sizeof(double) + 255) & ~(size_t)255; }
 static size_t fit_part_bytes(const FitKind& fk, int H, int W) { return ((size_t)fit_blocks_per_image(H, W) * fk.rec * sizeof(double) + 255) & ~(size_t)255; }
 
@@ -1085,7 +1101,7 @@ static std::vector<FitBatch> fit_batches(const FitKind& fk, int B, const int32_t
 
 static int fit_camera_run(const FitKind& fk, int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init,
                           int free_pp, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes,
-                          void* stream) {
+                          void* stream, float theta_max = 0.f) {
   int rc = fit_check_args(fk.name, B, hw, up, lat, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out);
   if (rc != PF_OK) return rc;
   const size_t need = fit_workspace_bytes(fk, B, hw);
@@ -1095,7 +1111,7 @@ static int fit_camera_run(const FitKind& fk, int device, int B, const int32_t* h
   if (rc != PF_OK) { g_create_error = err; return rc; }
   char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat};
+  const FitParams prm{free_pp, loss, huber_delta_deg, w_up, w_lat, theta_max};
   const std::vector<FitBatch> groups = fit_batches(fk, B, hw, up, lat, d_init, reinterpret_cast<double*>(base), base + fit_state_bytes(fk, B), d_out);
   // no host synchronisation: every image stops on its own flag, the launches run out as no-ops
   for (const FitBatch& fb : groups) fk.init(fb, prm, s);
@@ -1117,6 +1133,27 @@ size_t pf_fit_camera_usm_workspace_bytes(int B, const int32_t* hw) { return fit_
 int pf_fit_camera_usm(int device, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int loss,
                       float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes, void* stream) {
   return fit_camera_run(kFitUsm, device, B, hw, up, lat, d_init, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out, ws, ws_bytes, stream);
+}
+
+size_t pf_fit_fisheye_workspace_bytes(int B, const int32_t* hw) { return fit_workspace_bytes(kFitFisheye[0][0], B, hw); }
+
+int pf_fit_fisheye(int device, int kind, int B, const int32_t* hw, const float* const* up, const float* const* lat, const float* d_init, int free_pp, int poly,
+                   float theta_max, int loss, float huber_delta_deg, float w_up, float w_lat, int max_iter, float* d_out, void* ws, size_t ws_bytes,
+                   void* stream) {
+  const char* name = "pf_fit_fisheye";
+  if (kind != PF_FISHEYE_EQUIDISTANT && kind != PF_FISHEYE_EQUISOLID && kind != PF_FISHEYE_STEREOGRAPHIC) {
+    g_create_error = fmt("%s: unknown projection kind %d", name, kind);
+    return PF_ERR_ARG;
+  }
+  if (!(std::isfinite(theta_max) && theta_max > 0.f && theta_max < 3.14159265358979323846)) {
+    g_create_error = fmt("%s: theta_max must be finite and in (0, pi); got %g", name, (double)theta_max);
+    return PF_ERR_ARG;
+  }
+  const int rc = fit_check_args(name, B, hw, up, lat, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out);
+  if (rc != PF_OK) return rc;
+  if (poly != 0 && poly != 1) { g_create_error = fmt("%s: bad option (poly %d)", name, poly); return PF_ERR_ARG; }
+  return fit_camera_run(kFitFisheye[kind][poly], device, B, hw, up, lat, d_init, free_pp, loss, huber_delta_deg, w_up, w_lat, max_iter, d_out, ws, ws_bytes,
+                        stream, theta_max);
 }
 
 // pf_fit_camera_shared: the per-image fits' init and accumulate kernels over launch groups of FitBatch::MAX images, and per iteration one

@@ -395,13 +395,18 @@ void launch_paramnet_scalars(const float* raw, int nraw, float* out8, int B, int
 //   UsmFit (fit_camera_usm.hip, pf_fit_camera_usm): theta [6], the Unified Spherical Model's xi as one more parameter; out [n][PF_USMFIT_COLS]
 // FitParams::free_pp selects the fit of all of theta (otherwise cx, cy are held: 3 / 4 parameters).  Up to FitBatch::MAX images per launch,
 // per-image sizes and pointers in the kernel arguments; the strides of part, state, out and init are the model's
+//   FisheyeFit<KIND, POLY> (fit_camera_fisheye.hip, pf_fit_fisheye): theta [7], a fisheye lens of the compile-time projection KIND with k1, k2; POLY: k1, k2 are
+//   free, otherwise held: 3 / 5 parameters without POLY, 5 / 7 with it; out [n][PF_FISHFIT_COLS]
 struct PinholeFit;
 struct UsmFit;
-constexpr int FIT_STATE = 40, USMFIT_STATE = 48;  // Fit::STATE: doubles of per-image LM state
-constexpr int FIT_REC = 24, USMFIT_REC = 32;      // Fit::REC: doubles of one accumulate block's partial record
+template <int KIND, bool POLY>
+struct FisheyeFit;
+constexpr int FIT_STATE = 40, USMFIT_STATE = 48, FISHFIT_STATE = 64;  // Fit::STATE: doubles of per-image LM state
+constexpr int FIT_REC = 24, USMFIT_REC = 32, FISHFIT_REC = 40;        // Fit::REC: doubles of one accumulate block's partial record
 struct FitParams {
   int free_pp, loss;
   float huber_delta, w_up, w_lat;
+  float theta_max;  // the fisheye fit alone: the widest half field of view with a model value, radians; behind the fields every fit reads
 };
 struct FitBatch {
   static constexpr int MAX = 32;

@@ -83,6 +83,9 @@ _SIGNATURES = {
                                       _P]),
     "pf_pano_to_fisheye": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_float, _P, _P, _P, _P, _c.c_int, _P]),
     "pf_fisheye_fields": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _P, _P, _P]),
+    "pf_fit_fisheye_workspace_bytes": (_c.c_size_t, [_c.c_int, _P]),
+    "pf_fit_fisheye": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _c.c_int, _c.c_float, _c.c_float, _c.c_float,
+                                  _c.c_int, _P, _P, _c.c_size_t, _P]),
     "pf_yaw_moments_workspace_bytes": (_c.c_size_t, [_c.c_int, _P, _c.c_int, _P, _c.c_int, _c.c_int]),
     "pf_yaw_moments": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _P, _c.c_size_t, _P]),
     "pf_place_scores_workspace_bytes": (_c.c_size_t, [_c.c_int, _P, _c.c_int, _P, _c.c_int, _P, _c.c_int]),

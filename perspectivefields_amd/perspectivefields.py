@@ -32,7 +32,7 @@ from .schema import validate_state_dict
 from .synth import synthetic_state_dict
 
 # The geometry that needs no model lives in the sibling modules; every name that was reachable through this module still is.
-from .camera_fit import _FIT_COLS, _USMFIT_COLS, fit_camera_params, fit_camera_shared  # noqa: F401
+from .camera_fit import _FIT_COLS, _FISHFIT_COLS, _USMFIT_COLS, fisheye_lens_from_fit, fit_camera_params, fit_camera_shared, fit_fisheye_lens  # noqa: F401
 from .draw import DRAW_LAT, DRAW_UP, draw_camera, draw_perspective_fields  # noqa: F401
 from .field_metrics import _FERR_BINS, _FERR_BINS_PER_DEG, _FERR_COLS, _FERR_SUMS, FieldErrorAccumulator, field_errors  # noqa: F401
 from .fields import fields_from_params, general_vfov_to_focal  # noqa: F401
@@ -498,6 +498,27 @@ class PerspectiveFields(nn.Module):
             res = fit_camera_params(ups, lats, **kw)
         else:  # True: one camera; otherwise one label per image
             res = fit_camera_shared(ups, lats, None if shared is True else shared, **kw)
+        return res[0] if single else res
+
+    def fit_fisheye(self, preds, *, valid=None, **kw):
+        """A fisheye lens fitted to the dense fields of one inference() result (a dict) or of an inference_batch() list, on the GPU (see
+        fit_fisheye_lens for the options and the returned entries).  valid: the image circle -- one bool mask (H, W) of the fields' size for
+        every result, or one per result; the fields' pixels where it is False become NaN on the device before the fit, so they are skipped.
+        Returns new dicts; the inference results are not changed."""
+        single = isinstance(preds, dict)
+        plist = [preds] if single else list(preds)
+        ups, lats = PerspectiveFields._pred_fields(plist)
+        if valid is not None:
+            masks = [valid] * len(plist) if torch.is_tensor(valid) or isinstance(valid, np.ndarray) else list(valid)
+            if len(masks) != len(plist):
+                raise ValueError(f"fit_fisheye: valid has {len(masks)} masks for {len(plist)} results")
+            nan = float("nan")
+            for i, (u, l, m) in enumerate(zip(ups, lats, masks)):
+                m = torch.as_tensor(m).to(device=l.device, dtype=torch.bool)
+                if tuple(m.shape) != tuple(l.shape):
+                    raise ValueError(f"fit_fisheye: mask {i} is {tuple(m.shape)}, the fields are {tuple(l.shape)}")
+                ups[i], lats[i] = torch.where(m[None], u, torch.full_like(u, nan)), torch.where(m, l, torch.full_like(l, nan))
+        res = fit_fisheye_lens(ups, lats, **kw)
         return res[0] if single else res
 
     def field_errors(self, preds, up_gt, lat_gt, **kw):
