@@ -486,6 +486,58 @@ int pf_pano_compose(int device, int n_view, const void* const* h_view, const int
                     void* d_pano /*[n_pano][Hp][Wp][3]*/, float* d_weight /*[n_pano][Hp][Wp] or NULL*/,
                     float* d_acc /*[n_pano][Hp][Wp][4] fp32 workspace; may be NULL unless a panorama has more than 32 views*/, void* stream);
 
+/* Perspective fields transported between cameras of one centre, and from camera views onto equirectangular panoramas, on the device: the field
+ * counterparts of pf_reproject and pf_pano_compose (field_transport.hip).  Latitude is a property of the ray, so it is
+ * resampled.  An up vector is a tangent direction: it is lifted from the source's image plane to the sphere, rotated, and pushed to the destination's
+ * image plane through the differential of (unproject, rotate, project), in closed form for the Unified Spherical Model and the equirectangular
+ * projection (field_transport.h, no finite differences).  Gravity does not enter: the transport needs the relative rotation only, so predicted
+ * fields move exactly as labels do.
+ *   usm_push(X, t, xi)   the image direction of the tangent t at the ray X (any length): (t.x D - X.x s, t.y D - X.y s), D = X.z + xi |X|,
+ *                        s = t.z + xi (X . t) / |X|
+ *   usm_lift(X, m, xi)   the unit tangent t, t . X = 0, with usm_push(X, t, xi) a positive multiple of m: e1 = normalise(X x h), h = (1, 0, 0) where
+ *                        |X.x| < 0.9 |X|, else (0, 1, 0), e2 = (X / |X|) x e1; the 2 x 2 system alpha push(e1) + beta push(e2) = m by Cramer's rule
+ * Taps.  A sample at (u, v) in index units reads (floor v + {0, 1}, floor u + {0, 1}) with the bilinear weights.  A tap counts when it is inside the
+ * array and valid by pf_place_scores' rule (finite latitude, 1e-12 <= |up|^2 < inf); taps are NOT clamped.  W = the sum of the weights that count;
+ * sums in tap order in fp32.  Latitude lives on linspace(-c, size - c, size) (pf_fields_from_params' quirk): index j of a side of n sits at
+ * pixel-edge coordinate j n / (n - 1), so every side of a field, source or output of pf_reproject_fields, is >= 2.
+ *
+ * pf_reproject_fields: one source per output, batched like pf_reproject; cameras = rows of d_cam_src7 / d_cam_dst7 as there (RADIANS).  For
+ * destination pixel (row, col):
+ *   up    steps 1 to 5 of pf_reproject at (col + 1/2, row + 1/2): X_d, X_s = M X_d, (a_s, b_s), valid.  Taps at (a_s - 1/2, b_s - 1/2): W_u and
+ *         m = sum w_k u_k.  Valid iff step 5, W_u >= 1/2 and |m|^2 >= 1e-12.  t = usm_lift(X_s, m, xi_s); up' = normalise(usm_push(X_d, M^T t, xi_d))
+ *   lat   the same steps for the destination point (col W / (W - 1), row H / (H - 1)); taps at the source index (a_s (Ws - 1) / Ws,
+ *         b_s (Hs - 1) / Hs): W_l.  Valid iff step 5 and W_l >= 1/2.  lat' = sum w_k lat_k / W_l
+ * The pixel is written iff both parts are valid, else NaN x 3.  A non-finite camera parameter makes every pixel of that output NaN.
+ * h_src_up / h_src_lat = HOST arrays of n_src DEVICE pointers, fp32 planes [2][Hs][Ws] and [Hs][Ws]; h_src_hw = HOST [n_src][2]; h_src_index = HOST
+ * [batch].  d_up = DEVICE [batch][2][H][W], d_lat = DEVICE [batch][H][W], fp32, both required.
+ * Argument errors, in this order: no sources; a NULL field pointer; a source side < 2; batch < 1 or a NULL required pointer; H or W < 2; an index
+ * out of range; return PF_ERR_ARG before any device work with a message that begins "pf_reproject_fields".  One launch per 32 outputs on `stream`.
+ *
+ * pf_compose_fields: several views blended per panorama pixel; h_view_pano, d_cam7, n_pano, Hp, Wp, blend, d_weight as in pf_pano_compose.  For
+ * panorama pixel (row, col), D, lon, lat as there, and for view i of that panorama in the caller's order:
+ *   geometry   steps 1 to 5 of pf_pano_compose: X = M_i D, visible, (a, b), covered iff d > 0, weight w_i
+ *   taps       up at (a - 1/2, b - 1/2): W_u, m; latitude at the view's index (a (Ws - 1) / Ws, b (Hs - 1) / Hs): W_l, lat_i = sum w_k lat_k / W_l.
+ *              The panorama's own latitude grid is its pixel centres (pf_pano_fields)
+ *   up         t = M_i^T usm_lift(X, m, xi_i); p = (Wp / (2 pi) (t . e_lon) / cos lat, -Hp / pi (t . e_lat)), e_lon and e_lat of pf_pano_fields;
+ *              u_i = p / |p|
+ *   counts     iff covered, W_u >= 1/2, W_l >= 1/2, |m|^2 >= 1e-12 and 1e-12 <= |p|^2 < inf
+ * S = sum w_i, L = sum w_i lat_i, U = sum w_i u_i in fp32 in view order.  lat = L / S and up = U / |U| where S > 0 and |U|^2 >= 1e-12, else NaN x 3;
+ * d_weight, when given, holds S.  A view with a non-finite parameter contributes nothing and leaves every other bit unchanged.
+ * At most PF_COMPOSE_FIELDS_MAX_VIEWS views per panorama: more is PF_ERR_ARG (there is no accumulator path).  View sides >= 2; Hp, Wp >= 1.
+ * Argument errors, in this order: no views; a bad blend; a NULL field pointer; a view side < 2; n_pano < 1 or a NULL required pointer; Hp or Wp < 1;
+ * an index out of range or decreasing; more than 32 views of one panorama; return PF_ERR_ARG before any device work with a message that begins
+ * "pf_compose_fields".  Panoramas share launches of at most 32 views and 32 panoramas, on `stream`.
+ * Both: every comparison is a positive one, so NaN or infinite coordinates issue no load; no host synchronisation; stateless, no handle;
+ * deterministic, each output's bits independent of the batch it is in. */
+#define PF_COMPOSE_FIELDS_MAX_VIEWS 32
+int pf_reproject_fields(int device, int n_src, const float* const* h_src_up, const float* const* h_src_lat, const int32_t* h_src_hw /*[n_src][2]*/,
+                        int batch, const int32_t* h_src_index /*[batch]*/, const float* d_cam_src7 /*[batch][7]*/, const float* d_cam_dst7 /*[batch][7]*/,
+                        int H, int W, float* d_up /*[batch][2][H][W]*/, float* d_lat /*[batch][H][W]*/, void* stream);
+int pf_compose_fields(int device, int n_view, const float* const* h_view_up, const float* const* h_view_lat, const int32_t* h_view_hw /*[n_view][2]*/,
+                      const int32_t* h_view_pano /*[n_view], non-decreasing, in [0, n_pano)*/, const float* d_cam7 /*[n_view][7]*/, int n_pano, int Hp,
+                      int Wp, int blend /*PF_BLEND_FEATHER|PF_BLEND_MEAN*/, float* d_up /*[n_pano][2][Hp][Wp]*/, float* d_lat /*[n_pano][Hp][Wp]*/,
+                      float* d_weight /*[n_pano][Hp][Wp] or NULL*/, void* stream);
+
 /* Equirectangular panoramas rotated into equirectangular panoramas on the device, with the perspective fields of the panoramic camera:
  * levelling a tilted panorama, tilting an upright one (labelled data), re-centring a composite (pano_rotate.hip).
  * Conventions of pf_pano_crop and pf_pano_compose: x right, y down, z forward, world up = (0, -1, 0), R(r, p) = R_pitch(p) R_roll(r) camera ->

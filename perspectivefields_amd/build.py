@@ -18,13 +18,13 @@ ASAN = os.environ.get("PF_ASAN", "0") == "1"
 _VARIANT = ("_tune" if os.environ.get("PF_TUNING_BUILD", "0") == "1" else "") + ("_asan" if ASAN else "") + os.environ.get("PF_LIB_SUFFIX", "")
 LIBDIR = os.path.join(HERE, "lib" + _VARIANT)
 LIB = os.path.join(LIBDIR, "libpf_hip.so")
-SOURCES = ["igemm.hip", "igemm_sb.hip", "igemm_sbf.hip", "igemm_sbh.hip", "wino.hip", "attn.hip", "attn_block.hip", "stem7.hip", "thin_linear.hip", "elem.hip", "dw7.hip", "dw7_pk.hip", "cnx_mlp.hip", "mit_mlp.hip", "rb_gemm.hip", "rb_chain.hip", "cnx_rb.hip", "fit_camera.hip", "fit_camera_usm.hip", "fit_camera_fisheye.hip", "pano_crop.hip", "reproject.hip", "pano_compose.hip", "pano_rotate.hip", "gather_ss.hip", "cube_gather.hip", "fisheye_gather.hip", "fisheye_target.hip", "yaw_align.hip", "place_score.hip", "field_xform.hip", "draw_fields.hip", "composite.hip", "field_err.hip", "engine.hip", "engine_weights.hip", "engine_forward.hip", "engine_ops.hip", "geom_ops.hip"]
+SOURCES = ["igemm.hip", "igemm_sb.hip", "igemm_sbf.hip", "igemm_sbh.hip", "wino.hip", "attn.hip", "attn_block.hip", "stem7.hip", "thin_linear.hip", "elem.hip", "dw7.hip", "dw7_pk.hip", "cnx_mlp.hip", "mit_mlp.hip", "rb_gemm.hip", "rb_chain.hip", "cnx_rb.hip", "fit_camera.hip", "fit_camera_usm.hip", "fit_camera_fisheye.hip", "pano_crop.hip", "reproject.hip", "pano_compose.hip", "field_transport.hip", "pano_rotate.hip", "gather_ss.hip", "cube_gather.hip", "fisheye_gather.hip", "fisheye_target.hip", "yaw_align.hip", "place_score.hip", "field_xform.hip", "draw_fields.hip", "composite.hip", "field_err.hip", "engine.hip", "engine_weights.hip", "engine_forward.hip", "engine_ops.hip", "geom_ops.hip"]
 # dw7.hip: the scalar one-channel-per-lane kernel must not be SLP-vectorised (see the file header)
 # NO_PK_F32_FLAGS: these units are compiled without the packed-fp32 feature (pf_kernels.h PF_NO_PK_F32 says why); the x86 host pass prints an "ignoring feature"
 # line per function for it, filtered below
 NO_PK_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"dw7.hip": ["-fno-slp-vectorize"], "dw7_pk.hip": ["-fno-slp-vectorize"],
-               "attn_block.hip": NO_PK_F32_FLAGS, "stem7.hip": NO_PK_F32_FLAGS, "thin_linear.hip": NO_PK_F32_FLAGS, "cnx_mlp.hip": NO_PK_F32_FLAGS, "mit_mlp.hip": NO_PK_F32_FLAGS, "rb_gemm.hip": NO_PK_F32_FLAGS, "rb_chain.hip": NO_PK_F32_FLAGS, "cnx_rb.hip": NO_PK_F32_FLAGS, "fit_camera.hip": NO_PK_F32_FLAGS, "fit_camera_usm.hip": NO_PK_F32_FLAGS, "fit_camera_fisheye.hip": NO_PK_F32_FLAGS, "pano_crop.hip": NO_PK_F32_FLAGS, "reproject.hip": NO_PK_F32_FLAGS, "pano_compose.hip": NO_PK_F32_FLAGS, "pano_rotate.hip": NO_PK_F32_FLAGS, "gather_ss.hip": NO_PK_F32_FLAGS, "cube_gather.hip": NO_PK_F32_FLAGS, "fisheye_gather.hip": NO_PK_F32_FLAGS, "fisheye_target.hip": NO_PK_F32_FLAGS, "yaw_align.hip": NO_PK_F32_FLAGS, "place_score.hip": NO_PK_F32_FLAGS, "field_xform.hip": NO_PK_F32_FLAGS, "draw_fields.hip": NO_PK_F32_FLAGS, "composite.hip": NO_PK_F32_FLAGS, "field_err.hip": NO_PK_F32_FLAGS}
+               "attn_block.hip": NO_PK_F32_FLAGS, "stem7.hip": NO_PK_F32_FLAGS, "thin_linear.hip": NO_PK_F32_FLAGS, "cnx_mlp.hip": NO_PK_F32_FLAGS, "mit_mlp.hip": NO_PK_F32_FLAGS, "rb_gemm.hip": NO_PK_F32_FLAGS, "rb_chain.hip": NO_PK_F32_FLAGS, "cnx_rb.hip": NO_PK_F32_FLAGS, "fit_camera.hip": NO_PK_F32_FLAGS, "fit_camera_usm.hip": NO_PK_F32_FLAGS, "fit_camera_fisheye.hip": NO_PK_F32_FLAGS, "pano_crop.hip": NO_PK_F32_FLAGS, "reproject.hip": NO_PK_F32_FLAGS, "pano_compose.hip": NO_PK_F32_FLAGS, "field_transport.hip": NO_PK_F32_FLAGS, "pano_rotate.hip": NO_PK_F32_FLAGS, "gather_ss.hip": NO_PK_F32_FLAGS, "cube_gather.hip": NO_PK_F32_FLAGS, "fisheye_gather.hip": NO_PK_F32_FLAGS, "fisheye_target.hip": NO_PK_F32_FLAGS, "yaw_align.hip": NO_PK_F32_FLAGS, "place_score.hip": NO_PK_F32_FLAGS, "field_xform.hip": NO_PK_F32_FLAGS, "draw_fields.hip": NO_PK_F32_FLAGS, "composite.hip": NO_PK_F32_FLAGS, "field_err.hip": NO_PK_F32_FLAGS}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-gpu-rdc"]
 # PF_TUNING_BUILD=1: also compile the measured-and-rejected kernel variants and the ablation (no-load / no-store) kernels that
 # the scripts under scripts/ can select; the product build carries the default path and its parity alternatives only

@@ -1,5 +1,5 @@
 // Camera-geometry entry points of libpf_hip.so that take no pf_handle and use nothing of the engine (include/pf_hip.h): fields from parameters, the image
-// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip, fisheye_gather.hip, fisheye_target.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the pasting of objects (composite.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
+// gathers (pano_crop.hip, reproject.hip, pano_compose.hip, pano_rotate.hip, gather_ss.hip, cube_gather.hip, fisheye_gather.hip, fisheye_target.hip), the field transports (field_transport.hip), the yaw moments (yaw_align.hip), the placement scores (place_score.hip), the field transforms and the placement search (field_xform.hip), the drawing of fields (draw_fields.hip), the pasting of objects (composite.hip), the camera fits (fit_lm.h) and the field errors (field_err.hip).  Host-side argument checks and launch loops only.
 #include <type_traits>
 
 #include "host_pack.h"
@@ -396,6 +396,111 @@ int pf_pano_compose(int device, int n_view, const void* const* view, const int32
   }
   if (np > 0) launch(p0, np, v0, nv, 0u, 0u);
   if (hipGetLastError() != hipSuccess) { g_create_error = "pf_pano_compose: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+// The field transports (field_transport.hip): pf_reproject's and pf_pano_compose's launch loops with pairs of field planes as the sources.  NULL, or
+// what is wrong with the `n` sources (`noun`s) whose sides must be at least 2: the latitude grid needs size - 1 > 0
+static const char* field_sources_error(const char* noun, int n, const float* const* up, const float* const* lat, const int32_t* hw, std::string* why) {
+  for (int k = 0; k < n; ++k) {
+    if (!up[k] || !lat[k]) { *why = fmt("NULL field pointer of %s %d", noun, k); return why->c_str(); }
+    if (hw[2 * k] < 2 || hw[2 * k + 1] < 2) { *why = fmt("%s %d is %d x %d, smaller than 2 x 2", noun, k, hw[2 * k], hw[2 * k + 1]); return why->c_str(); }
+  }
+  return nullptr;
+}
+
+int pf_reproject_fields(int device, int n_src, const float* const* src_up, const float* const* src_lat, const int32_t* src_hw, int B, const int32_t* src_index,
+                        const float* d_cam_src7, const float* d_cam_dst7, int H, int W, float* d_up, float* d_lat, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_reproject_fields: " + m; return PF_ERR_ARG; };
+  std::string why;
+  if (n_src < 1 || !src_up || !src_lat || !src_hw) return bad("needs at least one source field (h_src_up, h_src_lat, h_src_hw)");
+  if (const char* e = field_sources_error("source", n_src, src_up, src_lat, src_hw, &why)) return bad(e);
+  if (B < 1 || !src_index || !d_cam_src7 || !d_cam_dst7 || !d_up || !d_lat) return bad("batch >= 1, h_src_index, d_cam_src7, d_cam_dst7, d_up and d_lat are required");
+  if (H < 2 || W < 2) return bad(fmt("output size %d x %d, smaller than 2 x 2", H, W));
+  for (int i = 0; i < B; ++i)
+    if (src_index[i] < 0 || src_index[i] >= n_src) return bad(fmt("output %d: source index %d of %d", i, src_index[i], n_src));
+  const int tpr = 16;  // a 64 x 16 pixel tile, as the other gathers
+  const long tiles_x = (W + 4 * tpr - 1) / (4 * tpr), tiles_y = (H + 256 / tpr - 1) / (256 / tpr);
+  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("output size %d x %d too large", H, W));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  const size_t npx = (size_t)H * W;
+  const int vec = (W % 4 == 0 && (misalign(d_up, 15) | misalign(d_lat, 15)) == 0) ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int i0 = 0; i0 < B; i0 += FieldReprojBatch::MAX) {
+    FieldReprojBatch rb;
+    rb.d = GatherDims{std::min(B - i0, (int)FieldReprojBatch::MAX), H, W, tpr, (int)tiles_x, (int)tiles_y, vec};
+    for (int k = 0; k < rb.d.n; ++k) {
+      const int p = src_index[i0 + k];
+      rb.src.up[k] = src_up[p]; rb.src.lat[k] = src_lat[p];
+      rb.src.H[k] = src_hw[2 * p]; rb.src.W[k] = src_hw[2 * p + 1];
+    }
+    rb.cam_src = d_cam_src7 + (size_t)i0 * 7;
+    rb.cam_dst = d_cam_dst7 + (size_t)i0 * 7;
+    rb.up = d_up + (size_t)i0 * 2 * npx;
+    rb.lat = d_lat + (size_t)i0 * npx;
+    launch_reproject_fields(rb, s);
+  }
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_reproject_fields: kernel launch failed"; return PF_ERR_DEVICE; }
+  return PF_OK;
+}
+
+// Panoramas share a launch while it holds at most FieldComposeBatch::MAX views and MAX panoramas, as in pf_pano_compose; a panorama of more views is
+// an argument error: there is no accumulator path
+int pf_compose_fields(int device, int n_view, const float* const* view_up, const float* const* view_lat, const int32_t* view_hw, const int32_t* view_pano,
+                      const float* d_cam7, int n_pano, int Hp, int Wp, int blend, float* d_up, float* d_lat, float* d_weight, void* stream) {
+  auto bad = [](const std::string& m) { g_create_error = "pf_compose_fields: " + m; return PF_ERR_ARG; };
+  constexpr int MAX = FieldComposeBatch::MAX;
+  std::string why;
+  if (n_view < 1 || !view_up || !view_lat || !view_hw) return bad("needs at least one view (h_view_up, h_view_lat, h_view_hw)");
+  if (blend != PF_BLEND_FEATHER && blend != PF_BLEND_MEAN) return bad(fmt("unknown blend %d", blend));
+  if (const char* e = field_sources_error("view", n_view, view_up, view_lat, view_hw, &why)) return bad(e);
+  if (n_pano < 1 || !view_pano || !d_cam7 || !d_up || !d_lat) return bad("n_pano >= 1, h_view_pano, d_cam7, d_up and d_lat are required");
+  if (Hp < 1 || Wp < 1) return bad(fmt("panorama size %d x %d", Hp, Wp));
+  std::vector<int> count(n_pano, 0);
+  for (int k = 0; k < n_view; ++k) {
+    if (view_pano[k] < 0 || view_pano[k] >= n_pano) return bad(fmt("view %d: panorama index %d of %d", k, view_pano[k], n_pano));
+    if (k > 0 && view_pano[k] < view_pano[k - 1]) return bad(fmt("view %d: panorama index %d after %d, the indices must not decrease", k, view_pano[k], view_pano[k - 1]));
+    ++count[view_pano[k]];
+  }
+  for (int p = 0; p < n_pano; ++p)
+    if (count[p] > MAX) return bad(fmt("panorama %d has %d views, more than %d views per panorama", p, count[p], MAX));
+  const int tpr = 16;  // a 64 x 16 pixel tile, as the other gathers
+  const long tiles_x = (Wp + 4 * tpr - 1) / (4 * tpr), tiles_y = (Hp + 256 / tpr - 1) / (256 / tpr);
+  if (tiles_x * tiles_y > INT32_MAX) return bad(fmt("panorama size %d x %d too large", Hp, Wp));
+  std::string err;
+  const int rc = check_device(device, &err);
+  if (rc != PF_OK) { g_create_error = err; return rc; }
+  const size_t npx = (size_t)Hp * Wp;
+  const int vec = (Wp % 4 == 0 && (misalign(d_up, 15) | misalign(d_lat, 15) | misalign(d_weight, 15)) == 0) ? 1 : 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  auto launch = [&](int p0, int np, int v0, int nv) {  // the panoramas [p0, p0 + np), whose views are [v0, v0 + nv)
+    FieldComposeBatch cb;
+    cb.d = GatherDims{np, Hp, Wp, tpr, (int)tiles_x, (int)tiles_y, vec};
+    for (int k = 0; k < nv; ++k) {
+      cb.src.up[k] = view_up[v0 + k]; cb.src.lat[k] = view_lat[v0 + k];
+      cb.src.H[k] = view_hw[2 * (v0 + k)]; cb.src.W[k] = view_hw[2 * (v0 + k) + 1];
+    }
+    cb.cam = d_cam7 + (size_t)v0 * 7;
+    for (int k = 0, f = 0; k < np; ++k) {
+      cb.first[k] = f;
+      cb.count[k] = count[p0 + k];
+      f += cb.count[k];
+    }
+    cb.up = d_up + (size_t)p0 * 2 * npx;
+    cb.lat = d_lat + (size_t)p0 * npx;
+    cb.weight = d_weight ? d_weight + (size_t)p0 * npx : nullptr;
+    launch_compose_fields(cb, blend, s);
+  };
+  int p0 = 0, np = 0, v0 = 0, nv = 0;  // the launch being filled
+  for (int p = 0, v = 0; p < n_pano; v += count[p], ++p) {
+    if (np > 0 && (nv + count[p] > MAX || np == MAX)) { launch(p0, np, v0, nv); np = nv = 0; }
+    if (np == 0) { p0 = p; v0 = v; }
+    ++np; nv += count[p];
+  }
+  if (np > 0) launch(p0, np, v0, nv);
+  if (hipGetLastError() != hipSuccess) { g_create_error = "pf_compose_fields: kernel launch failed"; return PF_ERR_DEVICE; }
   return PF_OK;
 }
 

@@ -661,6 +661,37 @@ struct ComposeBatch {
 void launch_pano_compose(const ComposeBatch& cb, int dtype, int blend, hipStream_t s);
 static_assert(offsetof(ComposeBatch, d) == 0 && offsetof(ComposeBatch, src) == 32, "ComposeBatch layout");
 
+// perspective fields transported between cameras of one centre and onto panoramas (field_transport.hip, include/pf_hip.h pf_reproject_fields /
+// pf_compose_fields): the gathers above with field planes as the sources
+struct FieldSources {  // of each output (pf_reproject_fields) or of each view of the launch (pf_compose_fields)
+  static constexpr int MAX = GatherSources::MAX;
+  const float* up[MAX];   // [2][Hs][Ws]
+  const float* lat[MAX];  // [Hs][Ws] degrees
+  int H[MAX], W[MAX];
+};
+struct FieldReprojBatch {
+  static constexpr int MAX = FieldSources::MAX;
+  GatherDims d;
+  FieldSources src;
+  const float* cam_src;  // [n][7]: roll, pitch, yaw (radians), rel_focal, rel_cx, rel_cy, xi
+  const float* cam_dst;  // [n][7]
+  float* up;             // [n][2][H][W]
+  float* lat;            // [n][H][W]
+};
+void launch_reproject_fields(const FieldReprojBatch& rb, hipStream_t s);
+struct FieldComposeBatch {
+  static constexpr int MAX = FieldSources::MAX;  // views of a launch, and of one panorama: there is no accumulator path
+  GatherDims d;       // n panoramas of Hp x Wp
+  FieldSources src;   // the launch's views
+  const float* cam;   // [views of the launch][7]
+  int first[MAX], count[MAX];
+  float* up;      // [n][2][Hp][Wp]
+  float* lat;     // [n][Hp][Wp]
+  float* weight;  // NULL or [n][Hp][Wp]: the summed weight S
+};
+void launch_compose_fields(const FieldComposeBatch& cb, int blend, hipStream_t s);
+static_assert(sizeof(FieldReprojBatch) <= 4096 && sizeof(FieldComposeBatch) <= 4096, "the field batches fit the kernel arguments");
+
 // relative yaw of views of one centre (yaw_align.hip, include/pf_hip.h pf_yaw_moments): the luminance planes of up to YawLum::MAX views per launch, then
 // the moments of up to YawBatch::MAX ordered pairs (a, b) per launch
 struct YawLum {

@@ -71,6 +71,8 @@ _SIGNATURES = {
     "pf_pano_crop": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     "pf_reproject": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _c.c_int, _c.c_float, _P, _P, _P, _P]),
     "pf_pano_compose": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P, _P, _P]),
+    "pf_reproject_fields": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _P, _P, _P, _c.c_int, _c.c_int, _P, _P, _P]),
+    "pf_compose_fields": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     "pf_pano_rotate": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     "pf_pano_fields": (_c.c_int, [_c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
     "pf_pano_crop_ss": (_c.c_int, [_c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _P]),

@@ -829,3 +829,132 @@ def compose_panorama(images, cams, *, height, width, pano_index=None, n_pano=Non
     head, c_idx = _source_args(dev, srcs, [sizes[i] for i in order], [idx[i] for i in order])
     _launch("pf_pano_compose", dev, head + (c_idx, cam.data_ptr(), P, Hp, Wp, _BLENDS[blend], fill, pano.data_ptr(), _ptr(weight), _ptr(acc)))
     return (pano, weight) if return_weight else pano
+
+
+def _field_sources(fn, up, lat, noun):
+    """the fields a transport takes as its sources, as the placement functions take them -- one pair up (2, h, w) / lat (h, w), a batched pair
+    (B, 2, h, w) / (B, h, w) or lists of pairs, CUDA tensors of one device, every side at least 2 (the latitude grid needs size - 1 > 0) ->
+    (n, the (h, w) of each field, device, a function that makes the n contiguous float32 (up, lat) pairs: the first thing that touches a device)"""
+    from .field_metrics import _field_list
+
+    _, ups, lats = _field_list(noun, up, lat, fn)
+    if not ups:
+        raise ValueError(f"{fn} needs at least one {noun} field")
+    if not all(torch.is_tensor(t) for t in ups + lats):
+        raise TypeError(f"{fn} takes torch tensors as fields")
+    if not all(t.is_cuda for t in ups + lats):
+        raise PfError(f"{fn} runs on the GPU only (no CPU path)")
+    for u, l in zip(ups, lats):
+        if u.dim() != 3 or u.shape[0] != 2 or min(u.shape[1:]) < 2 or tuple(l.shape) != tuple(u.shape[1:]):
+            raise ValueError(f"{fn}: up must be (2, h, w) and lat (h, w) with h, w >= 2; got {tuple(u.shape)} and {tuple(l.shape)}")
+    if len({t.device for t in ups + lats}) != 1:
+        raise ValueError(f"{fn}: all fields must be on one device")
+    dev = ups[0].device
+    dev = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+    make = lambda: ([u.to(torch.float32).contiguous() for u in ups], [l.to(torch.float32).contiguous() for l in lats])
+    return len(ups), [(int(u.shape[1]), int(u.shape[2])) for u in ups], dev, make
+
+
+def _field_head(dev, ups, lats, sizes):
+    """the head of a field transport's argument list: device, number of sources, their up and latitude pointers, their (h, w) pairs"""
+    n = len(ups)
+    return (dev.index, n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in ups]), (ctypes.c_void_p * n)(*[t.data_ptr() for t in lats]), _size_array(sizes))
+
+
+def reproject_fields(up, lat, src, dst, *, height=None, width=None, src_index=None, mode="deg"):
+    """Perspective fields of one camera -> the fields in another camera of the same centre on the GPU: `reproject_image` for fields, predicted ones
+    included.  The latitude is resampled (it belongs to the ray); an up vector is a tangent direction and is pushed through the differential of
+    (unproject, rotate, project), which needs the relative rotation only, not gravity.  Model: include/pf_hip.h pf_reproject_fields (DESIGN.md
+    section 38).  Exact fields of `src` come out as the exact fields of `dst` up to the bilinear interpolation error.
+
+    up (2, h, w), lat (h, w) in degrees (the layout of pred_gravity_original / pred_latitude_original): one field of CUDA tensors, a batched pair
+    (B, 2, h, w) / (B, h, w), or lists of pairs whose sizes may differ; every side at least 2.  src, dst, mode, src_index and the broadcasting are
+    exactly `reproject_image`'s, with the fields in the place of the images; height, width: the size of every output (at least 2 x 2), default the
+    sources'.  Four taps per pixel, not clamped: a tap outside the array or on an invalid pixel (a non-finite value, an up vector shorter than 1e-6)
+    is dropped, and a pixel is valid where the taps left carry at least half of the weight, for the up vector and for the latitude: NaN in all
+    three planes otherwise, and where the source camera does not see the pixel's ray.  So NaN is a mask that moves with the picture and does not
+    spread.  There is no `samples`: fields are smooth, and only a mask edge aliases.
+    Returns (up (B, 2, H, W) unit vectors, lat (B, H, W) degrees), float32.  GPU only: CPU tensors raise PfError."""
+    fn = "reproject_fields"
+    n, sizes, dev, make = _field_sources(fn, up, lat, "source")
+    if height is None or width is None:
+        if len(set(sizes)) != 1:
+            raise ValueError(f"{fn}: the fields differ in size; give height and width")
+    H, W = (int(v) for v in (sizes[0][0] if height is None else height, sizes[0][1] if width is None else width))
+    if H < 2 or W < 2:
+        raise ValueError(f"{fn}: output size must be at least 2 x 2; got {H} x {W}")
+    _check_mode(mode)
+    ts = _camera_params("src", src, fn) + _camera_params("dst", dst, fn)
+    Bp = _broadcast_len(fn, ts)
+    if src_index is not None:
+        idx = [operator.index(i) for i in (src_index.tolist() if torch.is_tensor(src_index) else src_index)]
+        if any(i < 0 or i >= n for i in idx):
+            raise ValueError(f"src_index entries must be in [0, {n})")
+    else:
+        idx = list(range(n)) if n > 1 else [0] * Bp
+    B = len(idx)
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one output")
+    if Bp not in (1, B):
+        raise ValueError(f"{fn}: camera parameters of length {Bp} for {B} outputs")
+    cam = _camera_rows(ts, (0, 1, 2, 7, 8, 9), B, dev, mode)
+    cam_s, cam_d = cam[:, :7].contiguous(), cam[:, 7:].contiguous()
+    ups, lats = make()
+    out_up = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+    out_lat = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    c_idx = (ctypes.c_int32 * B)(*idx)
+    _launch("pf_reproject_fields", dev, _field_head(dev, ups, lats, sizes) + (B, c_idx, cam_s.data_ptr(), cam_d.data_ptr(), H, W, out_up.data_ptr(), out_lat.data_ptr()))
+    return out_up, out_lat
+
+
+def compose_panorama_fields(up, lat, cams, *, height, width, pano_index=None, n_pano=None, blend="feather", mode="deg", return_weight=False):
+    """The perspective fields of camera views of one centre -> the fields of equirectangular panoramas on the GPU: `compose_panorama` for fields.
+    The way to dense fields of a 360 degree picture (`PerspectiveFields.inference_panorama`) and to one field out of several overlapping views.
+    Model: include/pf_hip.h pf_compose_fields; the result is laid out as `panorama_fields` lays out its labels.
+
+    up, lat: the views' fields as `reproject_fields` takes them (every side at least 2).  cams, height, width, pano_index, n_pano, blend, mode: as
+    `compose_panorama`, one camera per view.  Per panorama pixel every covering view gives a latitude and a unit up vector in the panorama's image
+    plane (taps and validity as `reproject_fields`); they are blended with the feather (or mean) weights, the up vectors as vectors and made
+    unit again.  A pixel that no view covers with valid fields is NaN in all three planes.  At most 32 views per panorama (a ValueError beyond).
+    Returns (up (n_pano, 2, Hp, Wp), lat (n_pano, Hp, Wp)) float32; with return_weight=True also the summed weight (n_pano, Hp, Wp), 0 where
+    nothing contributes.  GPU only: CPU tensors raise PfError."""
+    fn = "compose_panorama_fields"
+    n, sizes, dev, make = _field_sources(fn, up, lat, "view")
+    Hp, Wp = _out_size(height, width, "panorama size")
+    _check_mode(mode)
+    if blend not in _BLENDS:
+        raise ValueError(f"blend must be one of {tuple(_BLENDS)}; got {blend!r}")
+    ts = _camera_params("cams", cams, fn)
+    Bp = _broadcast_len(fn, ts)
+    if Bp not in (1, n):
+        raise ValueError(f"{fn}: camera parameters of length {Bp} for {n} views")
+    if pano_index is None:
+        idx = [0] * n
+    else:
+        idx = [operator.index(i) for i in (pano_index.tolist() if torch.is_tensor(pano_index) else pano_index)]
+        if len(idx) != n:
+            raise ValueError(f"pano_index has {len(idx)} entries for {n} views")
+        if any(i < 0 for i in idx):
+            raise ValueError("pano_index entries must be >= 0")
+    P = max(idx) + 1 if n_pano is None else operator.index(n_pano)
+    if P < 1 or any(i >= P for i in idx):
+        raise ValueError(f"pano_index entries must be in [0, {P}) (n_pano)")
+    counts = [0] * P
+    for i in idx:
+        counts[i] += 1
+    if max(counts) > _COMPOSE_MAX_VIEWS:
+        raise ValueError(f"{fn}: a panorama has {max(counts)} views, more than {_COMPOSE_MAX_VIEWS} views per panorama")
+    order = sorted(range(n), key=idx.__getitem__)   # stable: the caller's order within a panorama
+    cam = _camera_rows(ts, (0, 1, 2), n, dev, mode)
+    if order != list(range(n)):
+        cam = cam[torch.as_tensor(order, device=dev)]
+    cam = cam.contiguous()
+    ups, lats = make()
+    ups, lats = [ups[i] for i in order], [lats[i] for i in order]
+    out_up = torch.empty((P, 2, Hp, Wp), dtype=torch.float32, device=dev)
+    out_lat = torch.empty((P, Hp, Wp), dtype=torch.float32, device=dev)
+    weight = torch.empty((P, Hp, Wp), dtype=torch.float32, device=dev) if return_weight else None
+    c_idx = (ctypes.c_int32 * n)(*[idx[i] for i in order])
+    _launch("pf_compose_fields", dev, _field_head(dev, ups, lats, [sizes[i] for i in order]) + (c_idx, cam.data_ptr(), P, Hp, Wp, _BLENDS[blend], out_up.data_ptr(),
+                                                                                                 out_lat.data_ptr(), _ptr(weight)))
+    return (out_up, out_lat, weight) if return_weight else (out_up, out_lat)

@@ -37,9 +37,9 @@ from .draw import DRAW_LAT, DRAW_UP, draw_camera, draw_perspective_fields  # noq
 from .field_metrics import _FERR_BINS, _FERR_BINS_PER_DEG, _FERR_COLS, _FERR_SUMS, FieldErrorAccumulator, field_errors  # noqa: F401
 from .fields import fields_from_params, general_vfov_to_focal  # noqa: F401
 from .gathers import (BLEND_FEATHER, BLEND_MEAN, FISHEYE_LENS_FLOATS, FISHEYE_MAX_LENSES, FISHEYE_PROJECTIONS, GATHER_MAX_SAMPLES, PANO_F32, PANO_U8,  # noqa: F401
-                      _COMPOSE_MAX_VIEWS, _check_samples, _cuda_image_list, _fisheye_lens_table, compose_panorama, crop_cubemap, crop_fisheye, crop_panorama,
+                      _COMPOSE_MAX_VIEWS, _check_samples, _cuda_image_list, _fisheye_lens_table, compose_panorama, compose_panorama_fields, crop_cubemap, crop_fisheye, crop_panorama,
                       cubemap_face_cameras, cubemap_from_image, cubemap_to_image, cubemap_to_panorama, dual_fisheye_lenses, fisheye_fields, fisheye_lens, fisheye_to_panorama,
-                      panorama_fields, panorama_to_cubemap, panorama_to_fisheye, reproject_image, rotate_panorama)
+                      panorama_fields, panorama_to_cubemap, panorama_to_fisheye, reproject_fields, reproject_image, rotate_panorama)
 from .placement import COMPOSITE_HARD, COMPOSITE_SOFT, composite_objects, placement_scores, placement_search, transform_fields  # noqa: F401
 from .yaw import _YAW_MAX_CAND, align_yaw, gravity_from_views, yaw_scores, yaw_tree  # noqa: F401
 
@@ -593,7 +593,7 @@ class PerspectiveFields(nn.Module):
 
         return {k: column("pred_" + k) for k in ("roll", "pitch", "rel_focal", "rel_cx", "rel_cy", "xi")}
 
-    def rectify(self, images, preds, *, level="roll", undistort=True, rel_focal=None, height=None, width=None, **kw):
+    def rectify(self, images, preds, *, level="roll", undistort=True, rel_focal=None, height=None, width=None, fields=False, **kw):
         """The images warped with their recovered cameras, on the GPU (see reproject_image for `images`, the other options --
         src_index, fill, return_valid, return_map, samples -- and what is returned).  preds: one result dict, or a list of them, of inference*
         (a ParamNet model) or of fit_camera; the source camera is pred_roll, pred_pitch, pred_rel_focal, pred_rel_cx, pred_rel_cy and
@@ -603,7 +603,11 @@ class PerspectiveFields(nn.Module):
         gives it xi = 0 (a pinhole view), False keeps the source's xi.  rel_focal: its focal length (in heights of the output), default the
         source's.  height, width: the output size, default the images'.
         The perspective fields of the rectified view are `fields_from_params` of the destination camera (roll, pitch, rel_focal, 0, 0, xi
-        as stated here); they need no network."""
+        as stated here); they need no network.
+        fields=True additionally returns the PREDICTED dense fields of `preds` (pred_gravity_original, pred_latitude_original) in the destination
+        camera, transported by `reproject_fields` with the same cameras, src_index and output size: the result is then
+        (what reproject_image returns, (up (B, 2, H, W), lat (B, H, W))) -- what `draw_perspective_fields` draws over the rectified picture and
+        what `field_errors` scores against the destination's labels.  The default fields=False is the call as it was."""
         if level not in ("roll", "full", "none"):
             raise ValueError("level must be 'roll', 'full' or 'none'")
         if "mode" in kw:
@@ -611,7 +615,16 @@ class PerspectiveFields(nn.Module):
         src = PerspectiveFields._pred_cameras("rectify", preds)
         dst = dict(roll=src["roll"] if level == "none" else 0.0, pitch=0.0 if level == "full" else src["pitch"],
                    rel_focal=src["rel_focal"] if rel_focal is None else rel_focal, xi=0.0 if undistort else src["xi"])
-        return reproject_image(images, src, dst, height=height, width=width, mode="deg", **kw)
+        if not fields:
+            return reproject_image(images, src, dst, height=height, width=width, mode="deg", **kw)
+        plist = [preds] if isinstance(preds, dict) else list(preds)
+        up, lat = PerspectiveFields._pred_fields(plist)
+        out = reproject_image(images, src, dst, height=height, width=width, mode="deg", **kw)
+        size = (out[0] if isinstance(out, tuple) else out).shape[1:3]
+        index = kw.get("src_index")
+        if index is not None and len(plist) == len(index):   # one result per output: its fields are that output's source
+            index = None
+        return out, reproject_fields(up, lat, src, dst, height=int(size[0]), width=int(size[1]), src_index=index, mode="deg")
 
     def compose_panorama(self, images, preds, *, yaw=0.0, **kw):
         """The images placed on equirectangular panoramas with their recovered cameras, on the GPU (see compose_panorama for `images`, the
@@ -681,6 +694,50 @@ class PerspectiveFields(nn.Module):
         if not return_info:
             return out
         return out, {"roll": est["roll"], "pitch": est["pitch"], "views": views, "preds": preds, "gravity": est}
+
+    def inference_panorama(self, pano, *, n_yaw=8, view_pitch=(-45.0, 0.0, 45.0), vfov=100.0, view_size=None, blend="feather", height=None, width=None, samples=1):
+        """Dense perspective fields of a 360 degree equirectangular panorama, on the GPU.  The network sees pinhole-like inputs, so the panorama goes
+        through views: n_yaw x len(view_pitch) square pinhole views of `vfov` degrees are cut out of it (crop_panorama: yaw k 360 / n_yaw, the
+        pitches of view_pitch in degrees, roll 0, view_size pixels, default the network's input size) with cameras that are known in the panorama's
+        own frame, `inference_batch` runs on the device tensors, and `compose_panorama_fields` carries every view's predicted fields back onto the
+        equirectangular grid with those same crop cameras.  No fit is involved: the transport needs the crop cameras only, not gravity, so a tilted
+        panorama gives the fields of a tilted panoramic camera.
+        pano: one CUDA tensor (Hp, Wp, 3), uint8 or float32 (on the 0 .. 255 scale; the views go to the network as uint8).  At most 32 views.
+        blend: compose_panorama_fields' ("feather" or "mean"); height, width: the size of the result, default the panorama's; samples: the
+        antialiasing of the crops, 1 .. 4.
+        Returns a dict: pred_gravity_original (2, H, W), pred_latitude_original (H, W) degrees -- the layout `draw_perspective_fields` and
+        `field_errors` take -- and weight (H, W), the summed blend weight, 0 (fields NaN) where no view contributes."""
+        fn = "inference_panorama"
+        samples = _check_samples(fn, samples)
+        n_yaw = operator.index(n_yaw)
+        pitches = [float(v) for v in (view_pitch if isinstance(view_pitch, (list, tuple)) else [view_pitch])]
+        if n_yaw < 1 or not pitches:
+            raise ValueError(f"{fn} needs n_yaw >= 1 and at least one view pitch")
+        if n_yaw * len(pitches) > _COMPOSE_MAX_VIEWS:
+            raise ValueError(f"{fn}: {n_yaw * len(pitches)} views, at most {_COMPOSE_MAX_VIEWS}")
+        if not (0.0 < float(vfov) < 180.0):
+            raise ValueError("vfov must be in (0, 180) degrees")
+        if blend not in ("feather", "mean"):
+            raise ValueError(f"blend must be 'feather' or 'mean'; got {blend!r}")
+        size = NET_H if view_size is None else int(view_size)
+        if size < 8:
+            raise ValueError("view_size must be at least 8")
+        if (height is None) != (width is None):
+            raise ValueError(f"{fn}: height and width are both given or both left out")
+        if not torch.is_tensor(pano):
+            raise TypeError(f"{fn} takes one panorama, a torch tensor (Hp, Wp, 3)")
+        _cuda_image_list(fn, [pano], ("panorama", "panoramas"), "a panorama must be (Hp, Wp, 3) with Hp, Wp >= 2", 2)
+        Hp, Wp = (int(pano.shape[0]), int(pano.shape[1])) if height is None else (int(height), int(width))
+        if Hp < 1 or Wp < 1:
+            raise ValueError(f"{fn}: the result must be at least 1 x 1; got {Hp} x {Wp}")
+        cams = dict(roll=0.0, pitch=[p for p in pitches for _ in range(n_yaw)], yaw=[k * 360.0 / n_yaw for _ in pitches for k in range(n_yaw)],
+                    rel_focal=0.5 / math.tan(math.radians(float(vfov)) / 2))
+        crops = crop_panorama(pano, cams["roll"], cams["pitch"], cams["rel_focal"], yaw=cams["yaw"], height=size, width=size, fields=False, samples=samples)[0]
+        if crops.dtype != torch.uint8:
+            crops = crops.round().clamp(0, 255).to(torch.uint8)
+        up, lat = PerspectiveFields._pred_fields(self.inference_batch(list(crops)))
+        up, lat, weight = compose_panorama_fields(up, lat, cams, height=Hp, width=Wp, blend=blend, mode="deg", return_weight=True)
+        return {"pred_gravity_original": up[0], "pred_latitude_original": lat[0], "weight": weight[0]}
 
     def forward(self, batched_inputs) -> List[dict]:
         """batched_inputs: list of {"image": (3,320,320) float BGR 0..255, "height", "width"} (reference :223-272)."""
